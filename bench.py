@@ -7,9 +7,20 @@
        WORLD_SIZE != N, or fewer than N visible GPUs: exit code 2 with the reason on stderr.
   python bench.py --infer [--infer-bs 32]   BASELINE.json configs[1]: batched inference (uint8 -> eval forward
                                             -> decode -> NMS) as its own JSON line
+  --full              everything else the bench measures, each still under its own switch: the per-kernel roofline
+                      (--roofline-steps), the DDP-staged step (--stage-check), the CPU baseline (--no-cpu-baseline,
+                      --cpu-budget), the configs[1] inference / NMS objects (--infer-steps), the augmentation chain
+                      (--augment-bench) and the configs[4] l-scale object (--lscale-steps). Without --full none of
+                      them runs and their fields of the line are null: set-up, warm-up, the K timed steps, the line.
+  --dump-outputs DIR  after the timed steps, write what the last timed step computed as DIR/<name>.npy (float32;
+                      rank 0): the loss items step() returned and the model / EMA state it left (--infer: the
+                      padded detections and their counts). Larger outputs are cut to a fixed, seeded sample.
+                      So that two runs write the same arrays, the last timed step of a training run then starts
+                      from the seeded initial state (restored in stream order right before it): the atomics of the
+                      DCN backward make runs differ in the last bit, which training would amplify step by step.
 
-Prints ONE JSON line on rank 0 (value = images/s summed over all ranks; max-over-ranks timing). The training line
-also carries a short configs[1] inference measurement under "inference" (rank 0, N=1 only).
+Prints ONE JSON line on rank 0 (value = images/s summed over all ranks; max-over-ranks timing). With --full the
+training line also carries a short configs[1] inference measurement under "inference" (rank 0, N=1 only).
 """
 from __future__ import annotations
 
@@ -29,6 +40,55 @@ CFG = ROOT / "tests" / "configs" / "yolo11-701-YOLO-AD-Refine.yaml"
 HBM_PEAK_GBS = 8000.0      # MI355X_MICROARCH.md chip table (spec)
 BF16_MFMA_PEAK_TF = 2500.0  # dense bf16 MFMA (spec, no sparsity)
 F32_MFMA_PEAK_TF = 157.3
+DUMP_BUDGET_BYTES = 48 << 20  # --dump-outputs: the arrays of one run together (64 MB is the limit)
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: {name: tensor} -> DIR/<name>.npy as float32. When the arrays together exceed
+    DUMP_BUDGET_BYTES, each one above its equal share is cut to that many elements at sorted indices drawn without
+    replacement from numpy's default_rng(0): the same elements in every run with the same arguments."""
+    import numpy as np
+    import torch
+    d = Path(dirname)
+    d.mkdir(parents=True, exist_ok=True)
+    over = 4 * sum(t.numel() for t in arrays.values()) > DUMP_BUDGET_BYTES
+    share = DUMP_BUDGET_BYTES // 4 // max(1, len(arrays))
+    for name, t in arrays.items():
+        t = t.detach()
+        if over and t.numel() > share:
+            idx = np.sort(np.random.default_rng(0).choice(t.numel(), share, replace=False))
+            t = t.reshape(-1)[torch.from_numpy(idx).to(t.device)]
+        np.save(d / f"{name}.npy", t.float().cpu().numpy())
+
+
+def train_state(tr):
+    """Every device tensor a FusedTrainer.step reads and updates in place: the model's parameters and buffers (BN
+    statistics, the dropout seeds), the gradient arena, the momentum buffers and the EMA."""
+    live = list(tr.model.parameters()) + list(tr.model.buffers()) + [tr.grad, tr.mom]
+    return live + ([tr.ema_flat] if tr.use_ema else [])
+
+
+def restore_state(live, snap):
+    """Copy a snapshot of train_state back, in stream order (one grouped copy for the floating tensors)."""
+    import torch
+    with torch.no_grad():
+        fl = [(t, s) for t, s in zip(live, snap) if t.dtype.is_floating_point]
+        torch._foreach_copy_([t for t, _ in fl], [s for _, s in fl])
+        for t, s in zip(live, snap):
+            if not t.dtype.is_floating_point:
+                t.copy_(s)
+
+
+def train_outputs(tr, items):
+    """What one FusedTrainer.step leaves its caller: the loss items it returns, and the state it updates in place
+    (every floating state_dict entry of the model and of the EMA, flattened and joined in state_dict order)."""
+    import torch
+    state = {k: v for k, v in tr.model.state_dict().items() if v.dtype.is_floating_point}
+    out = {"loss_items": items, "model_state": torch.cat([v.detach().float().reshape(-1) for v in state.values()])}
+    if tr.use_ema:
+        ema = tr.ema_state_dict()
+        out["ema_state"] = torch.cat([ema[k].reshape(-1) for k in state])
+    return out
 
 
 def cpu_baseline(bs=2, img=640, budget_s=20.0):
@@ -95,13 +155,13 @@ def cpu_baseline_infer(bs=1, img=640, budget_s=8.0):
 
 
 def infer_bench(model, bs, img, steps, warmup, dev, graph=True, roofline=False, conf=0.25, multi_label=False,
-                nms_share=False):
+                nms_share=False, keep=None):
     """BASELINE.json configs[1]: uint8 batch -> /255 in the stem -> eval forward (bf16) -> decode -> NMS
     (predictor settings conf 0.25, iou 0.7, max_det 300; or the validator's conf 0.001 + multi-label,
     engine/validator.py:98-99), one hipGraph per batch. Inputs resident in HBM; the timed region is `steps` graph
     replays between two synchronisations. Returns (images/s, ms/batch, roofline or None, detections per batch,
     NMS share or None): the share is the adr_nms launches' part of one eagerly timed batch (HIP events per
-    launch)."""
+    launch). `keep`, a dict, receives the last timed batch's padded detections and counts (copies)."""
     import torch
     import adrefine.kernels as K
     from adrefine.data.synthetic import images_u8
@@ -120,6 +180,8 @@ def infer_bench(model, bs, img, steps, warmup, dev, graph=True, roofline=False, 
         out, n = pred.run_padded(x)
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
+    if keep is not None:
+        keep.update(detections=out.clone(), counts=n.clone())
     roof = share = None
     if roofline or nms_share:
         g, pred.graph = pred.graph, None
@@ -417,7 +479,15 @@ def main():
     ap.add_argument("--share-gpu", action="store_true",
                     help="tests only (with --ddp-backend gloo): every rank on GPU rank %% visible, so the N-rank "
                          "launch path runs on a one-GPU box")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs beside the headline figure (roofline, DDP staging, CPU baseline, "
+                         "inference / NMS, augmentation, l-scale), each under its own switch")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float32)")
     args = ap.parse_args()
+    if not args.full:  # a plain run: set-up, warm-up, the timed steps, the line
+        args.no_cpu_baseline = True
+        args.roofline_steps = args.stage_check = args.infer_steps = args.augment_bench = args.lscale_steps = 0
     if args.share_gpu and args.ddp_backend != "gloo":
         print("bench.py: --share-gpu needs --ddp-backend gloo (RCCL refuses two ranks on one GPU)", file=sys.stderr)
         sys.exit(2)
@@ -455,10 +525,13 @@ def main():
         cfg["scale"] = args.scale
         model = DetectionModel(cfg, compute_dtype=dtype).to(dev)
     if args.infer:
+        last = {} if args.dump_outputs and rank == 0 else None
         ips, ms, roof, dets, _ = infer_bench(model, args.infer_bs, args.img, args.steps, args.warmup, dev,
-                                             graph=not args.no_graph, roofline=True)
+                                             graph=not args.no_graph, roofline=args.full, keep=last)
         if roof is not None:
             roof["traffic"], roof["traffic_source"] = None, None
+        if last is not None:
+            dump_outputs(args.dump_outputs, last)
         if rank == 0:
             cpu = None if args.no_cpu_baseline else cpu_baseline_infer()
             print(json.dumps({
@@ -480,6 +553,14 @@ def main():
             dist.broadcast(p.data, 0)
     # the reference's batch_size is the GLOBAL batch (trainer.py:290, 305-306): accumulate and weight decay
     tr = FusedTrainer(model, batch_size=world * args.bs, world_size=world)
+    # --dump-outputs: the DCN backward accumulates with float atomics, so two runs' gradients differ in the last bit,
+    # and training amplifies that from step to step (the assigner's choices flip) until the states have nothing in
+    # common. The last timed step therefore starts from the seeded initial state, put back in stream order right
+    # before it: what it computes then depends on the arguments alone, to within one step's rounding.
+    live = snap = None
+    if args.dump_outputs:
+        live = train_state(tr)
+        snap = [t.detach().clone() for t in live]
     # rank's shard of the stream, as the dataloader yields it: uint8 images (preprocess_batch's /255 runs inside the
     # step, fused into the stem kernels) + COCO-shape labels
     batch, _ = train_batch(args.bs, args.img, seed=1000 * rank, device=dev, u8=not args.float_images)
@@ -497,6 +578,8 @@ def main():
     t0 = time.perf_counter()
     ev[0].record()
     for k in range(args.steps):
+        if snap is not None and k == args.steps - 1:
+            restore_state(live, snap)
         items = tr.step(batch)
         ev[k + 1].record()  # per-step boundaries on the step's stream (median / p90; the value uses the wall clock)
     t_host = time.perf_counter() - t0  # host-side enqueue time (launch-bound if close to the step time)
@@ -505,6 +588,8 @@ def main():
         dist.barrier()
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:  # before anything below steps the model again
+        dump_outputs(args.dump_outputs, train_outputs(tr, items))
     # per-kernel durations for the roofline: HIP events on the launch stream around every conv-GEMM launch of
     # the same step, run eagerly right after the timed replays (a graph replay cannot be split per kernel)
     peak_gib = torch.cuda.max_memory_allocated(dev) / 2 ** 30  # caching-allocator peak over warmup + capture + steps

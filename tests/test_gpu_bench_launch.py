@@ -35,7 +35,7 @@ def test_bench_gpus2_on_one_gpu_refused():
 def test_bench_gpus2_self_launch_gloo_shared_gpu():
     r = _bench(["--gpus", "2", "--ddp-backend", "gloo", "--share-gpu", "--steps", "3", "--warmup", "2", "--bs", "4",
                 "--img", "320", "--no-cpu-baseline", "--stage-check", "0", "--augment-bench", "0",
-                "--infer-steps", "0", "--roofline-steps", "1"], 400)
+                "--infer-steps", "0", "--full", "--roofline-steps", "1"], 400)
     assert r.returncode == 0, (r.returncode, r.stdout[-2000:], r.stderr[-4000:])
     assert "DDP: launching" in r.stderr and "torch.distributed.run" in r.stderr
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
