@@ -551,6 +551,28 @@ int adr_dcn_bwd_bf16_levels(const adr_dcn_level* lv, int levels, int xcs, int om
 int adr_augment_u8(const void* pool, const void* descs, int B, const int* tables, const void* luts, void* out, int H,
                    int W, void* stream);
 int adr_augment_desc_size(void);
+/* LetterBox pixels (data/augment.py:1475-1640; the validation transform data/dataset.py:181, RandomPerspective's
+ * pre_transform after close_mosaic, the predictor's pre_transform + preprocess engine/predictor.py:125, 144-156):
+ * cv2.resize(INTER_LINEAR) to the unpadded size -> cv2.copyMakeBorder(constant 114) -> optional BGR -> RGB ->
+ * CHW, one launch for B source images of different sizes into out (B, 3, H, W) uint8. pool: the sources (HWC BGR
+ * uint8) packed as for adr_augment_u8 (pool_bytes long); descs: B device adr_letterbox_desc records {int64 byte
+ * offset; int sw, sh, nw, nh, left, top, mode, tab_off, rgb, pad; size adr_letterbox_desc_size()} and descs_host the
+ * same records in host memory (validated here: sizes > 0, nw <= W - left, nh <= H - top, source inside the pool,
+ * tables inside `tables`). nw == 0: the image is filled with 114 (an empty slot of a partly filled batch). mode: 0
+ * copy (sw == nw, sh == nh), 1 linear, 2 the 2 x 2 average OpenCV's INTER_LINEAR takes when sw == 2 nw and sh == 2 nh.
+ * tables (ntab ints): per linear image, at tab_off, sx[nw], a0[nw], a1[nw], sy[nh], b0[nh], b1[nh]: OpenCV's 8-bit
+ * fixed-point resize coefficients (11 bits) computed on the host (adrefine/data/augment.py); the kernel is integer
+ * only. OpenCV is not installed: the resize is restated from OpenCV 4.x's published algorithm and is PARITY UNPINNED
+ * against real OpenCV, as warpAffine and cvtColor of adr_augment_u8 are. */
+int adr_letterbox_u8(const void* pool, size_t pool_bytes, const void* descs, const void* descs_host, int B,
+                     const int* tables, int ntab, void* out, int H, int W, void* stream);
+int adr_letterbox_desc_size(void);
+/* ops.scale_boxes + clip_boxes (utils/ops.py:88-123, 315-334) in place on boxes (B, rows, cols >= 4) fp32, e.g. the
+ * padded NMS output (B, max_det, 6): for the first four columns x = (x - pad) / gain (a true IEEE fp32 division,
+ * as torch's `boxes /= gain`), then clamped to [0, w0] / [0, h0]. table: B device rows {gain, padx, pady, w0, h0}
+ * fp32. Rows r >= counts[b] stay untouched (counts NULL: every row). xywh != 0: columns 2, 3 keep their pad. */
+int adr_scale_boxes(float* boxes, const int* counts, const float* table, int B, int rows, int cols, int xywh,
+                    void* stream);
 /* W (Cout, C, 3, 3) fp32 -> [(tap*C + c)][Cout] operand for dcols = dy x W. */
 int adr_dcn_weight_t(int dtype, const float* w, void* out, int Cout, int C, void* stream);
 /* Per-image 2-layer gate MLP on pooled vectors: out = act2(W2 act1(W1 (in*in_scale) + b1) + b2);

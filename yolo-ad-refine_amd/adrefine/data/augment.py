@@ -12,11 +12,19 @@ the reference never exist.
 Covered (detection, the default hyp of cfg/default.yaml and any degrees / translate / scale / shear / flip / HSV
 gains): Mosaic (n=4, p=1), CopyPaste (p=0 or no segments), RandomPerspective (perspective 0: warpAffine), MixUp
 (p=0), Albumentations (absent package: no-op, as in the reference without albumentations installed), RandomHSV,
-RandomFlip, Format. Not covered (raise): LetterBox / close_mosaic (cv2.resize), warpPerspective, MixUp or
-CopyPaste with p > 0, mosaic9, segments / keypoints. Source images come in resized as BaseDataset.load_image leaves
-them (data/base.py:151-190); decoding and that resize stay on the host."""
+RandomFlip, Format; LetterBox (every constructor argument; rect_shape, ratio_pad and the label update), as
+RandomPerspective's pre_transform when mosaic is off (mosaic p < 1, close_mosaic), as the validation transform
+(build_transforms with augment off) and on raw images of any size (render_letterbox, FusedPredictor.predict_images).
+A LetterBox that only pads (the shape already equals new_unpad: every dataset-fed image, since
+BaseDataset.load_image leaves the long side at imgsz) is a canvas with one tile and goes through adr_augment_u8 with
+the rest of the chain; a LetterBox that resizes is rendered by adr_letterbox_u8 (csrc/adr_letterbox.hip: cv2.resize
+INTER_LINEAR in OpenCV's fixed point + constant border + RGB / CHW). Not covered (raise): a LetterBox resize followed
+by warp / HSV / flip in one plan (cannot arise from a dataset), warpPerspective, MixUp or CopyPaste with p > 0,
+mosaic9, segments / keypoints. Source images come in resized as BaseDataset.load_image leaves them
+(data/base.py:151-190); decoding and that resize stay on the host."""
 from __future__ import annotations
 
+import copy
 import ctypes
 import math
 import random
@@ -27,12 +35,14 @@ import torch
 from .instance import Instances
 
 __all__ = ["ImagePlan", "Compose", "Mosaic", "CopyPaste", "RandomPerspective", "MixUp", "Albumentations", "RandomHSV",
-           "RandomFlip", "Format", "v8_transforms", "collate_fn", "render", "warp_affine_tables"]
+           "RandomFlip", "LetterBox", "Format", "v8_transforms", "build_transforms", "close_mosaic", "collate_fn",
+           "render", "render_letterbox", "warp_affine_tables", "resize_linear_tables"]
 
 
 class ImagePlan:
     """A deferred uint8 BGR HWC image (see the module docstring). Stages must come in the chain's order:
-    canvas (source / mosaic) -> warp -> hsv -> flips -> channel order."""
+    canvas (source / mosaic / letterbox) -> warp -> hsv -> flips -> channel order. A letterbox that resizes is a
+    stage of its own (`resize`), followed by the channel order only."""
 
     def __init__(self, src: np.ndarray):
         if src.dtype != np.uint8 or src.ndim != 3 or src.shape[2] != 3:
@@ -41,6 +51,8 @@ class ImagePlan:
         self.tiles = [(src, 0, 0, w, h, 0, 0)]  # (source, x1a, y1a, x2a, y2a, x1b, y1b) on the canvas
         self.canvas = (w, h)
         self.size = (w, h)  # current (w, h)
+        self.resize = None  # (nw, nh, left, top): LetterBox's cv2.resize of the canvas to (nw, nh), placed at (left, top)
+        self.ratio_pad = None  # LetterBox: ((ratio_w, ratio_h), (left, top))
         self.M = None  # 2x3 float32 warpAffine matrix (canvas -> output)
         self.lut = None  # (3, 256) uint8
         self.flip_ud = self.flip_lr = False
@@ -51,8 +63,33 @@ class ImagePlan:
         return (self.size[1], self.size[0], 3)
 
     def _stage(self, ok, what):
+        if self.resize is not None:
+            raise NotImplementedError(f"ImagePlan: {what} after a LetterBox that resizes (cv2.resize is not fused into "
+                                      "the later stages; images from a dataset are already at new_unpad: pad only)")
         if not ok:
             raise NotImplementedError(f"ImagePlan: {what} out of the supported chain order")
+
+    def letterbox(self, new_unpad, left, top, right, bottom):
+        """The plan of cv2.copyMakeBorder(cv2.resize(image, new_unpad) if its size differs, top, bottom, left, right,
+        114) (LetterBox, augment.py:1583-1589) — a new plan; this one is unchanged."""
+        self._stage(self.M is None and self.lut is None and not (self.flip_ud or self.flip_lr), "letterbox")
+        q = copy.copy(self)
+        w, h = self.size
+        nw, nh = (int(v) for v in new_unpad)
+        if (w, h) == (nw, nh):  # pad only: the canvas grows, its tiles move
+            q.tiles = [(s, x1a + left, y1a + top, x2a + left, y2a + top, x1b, y1b)
+                       for s, x1a, y1a, x2a, y2a, x1b, y1b in self.tiles]
+            q.canvas = q.size = (w + left + right, h + top + bottom)
+        else:
+            src = self.tiles[0][0] if len(self.tiles) == 1 else None
+            if src is None or self.tiles[0][1:] != (0, 0, src.shape[1], src.shape[0], 0, 0) or self.canvas != (w, h):
+                raise NotImplementedError("ImagePlan: a LetterBox resize of anything but one whole source image")
+            if nw <= 0 or nh <= 0:
+                raise ValueError(f"LetterBox: empty resized image {nw} x {nh}")
+            q.tiles = list(self.tiles)
+            q.resize = (nw, nh, left, top)
+            q.size = (nw + left + right, nh + top + bottom)
+        return q
 
 
 def _plan(img):
@@ -131,7 +168,7 @@ class Mosaic(BaseMixTransform):
         for i in range(4):
             patch = labels if i == 0 else labels["mix_labels"][i - 1]
             src = _plan(patch["img"])
-            if len(src.tiles) != 1 or src.M is not None or src.lut is not None:
+            if len(src.tiles) != 1 or src.M is not None or src.lut is not None or src.resize is not None:
                 raise NotImplementedError("Mosaic tiles must be untransformed source images")
             img = src.tiles[0][0]
             h, w = patch.pop("resized_shape")
@@ -267,7 +304,7 @@ class RandomPerspective:
 
     def __call__(self, labels):
         if self.pre_transform and "mosaic_border" not in labels:
-            raise NotImplementedError("RandomPerspective pre_transform (LetterBox: mosaic p < 1 / close_mosaic)")
+            labels = self.pre_transform(labels)
         labels.pop("ratio_pad", None)
         img = _plan(labels["img"])
         cls = labels["cls"]
@@ -338,13 +375,74 @@ class RandomFlip:
         h = 1 if instances.normalized else h
         w = 1 if instances.normalized else w
         if self.direction == "vertical" and random.random() < self.p:
+            img._stage(True, "flip")
             img.flip_ud = not img.flip_ud
             instances.flipud(h)
         if self.direction == "horizontal" and random.random() < self.p:
+            img._stage(True, "flip")
             img.flip_lr = not img.flip_lr
             instances.fliplr(w)
         labels["img"] = img
         labels["instances"] = instances
+        return labels
+
+
+class LetterBox:
+    """augment.py:1475-1640: the reference's arithmetic in the reference's order; the image becomes an ImagePlan
+    (pad only: a canvas with the image at (left, top); otherwise a resize stage for adr_letterbox_u8)."""
+
+    def __init__(self, new_shape=(640, 640), auto=False, scaleFill=False, scaleup=True, center=True, stride=32):
+        self.new_shape = new_shape
+        self.auto = auto
+        self.scaleFill = scaleFill
+        self.scaleup = scaleup
+        self.stride = stride
+        self.center = center
+
+    def __call__(self, labels=None, image=None):
+        """labels -> labels with labels["img"] the letterboxed plan; image= alone -> the plan
+        (plan.ratio_pad = ((ratio_w, ratio_h), (left, top)))."""
+        if labels is None:
+            labels = {}
+        img = _plan(labels.get("img") if image is None else image)
+        shape = img.shape[:2]  # current shape [height, width]
+        new_shape = labels.pop("rect_shape", self.new_shape)
+        if isinstance(new_shape, int):
+            new_shape = (new_shape, new_shape)
+        r = min(new_shape[0] / shape[0], new_shape[1] / shape[1])
+        if not self.scaleup:
+            r = min(r, 1.0)
+        ratio = r, r
+        new_unpad = int(round(shape[1] * r)), int(round(shape[0] * r))
+        dw, dh = new_shape[1] - new_unpad[0], new_shape[0] - new_unpad[1]
+        if self.auto:
+            dw, dh = np.mod(dw, self.stride), np.mod(dh, self.stride)
+        elif self.scaleFill:
+            dw, dh = 0.0, 0.0
+            new_unpad = (new_shape[1], new_shape[0])
+            ratio = new_shape[1] / shape[1], new_shape[0] / shape[0]
+        if self.center:
+            dw /= 2
+            dh /= 2
+        top, bottom = int(round(dh - 0.1)) if self.center else 0, int(round(dh + 0.1))
+        left, right = int(round(dw - 0.1)) if self.center else 0, int(round(dw + 0.1))
+        out = img.letterbox(new_unpad, left, top, right, bottom)
+        out.ratio_pad = (ratio, (left, top))
+        if labels.get("ratio_pad"):
+            labels["ratio_pad"] = (labels["ratio_pad"], (left, top))  # for evaluation
+        if len(labels):
+            labels["img"] = img  # _update_labels denormalises with the shape before the letterbox
+            labels = self._update_labels(labels, ratio, dw, dh)
+            labels["img"] = out
+            labels["resized_shape"] = new_shape
+            return labels
+        return out
+
+    def _update_labels(self, labels, ratio, padw, padh):
+        labels["instances"].convert_bbox(format="xyxy")
+        labels["instances"].denormalize(*labels["img"].shape[:2][::-1])
+        labels["instances"].scale(*ratio)
+        labels["instances"].add_padding(padw, padh)
         return labels
 
 
@@ -381,7 +479,8 @@ def v8_transforms(dataset, imgsz, hyp, stretch=False):
     """augment.py:2273-2335 (detection: no keypoints, copy_paste_mode 'flip' or p = 0)."""
     mosaic = Mosaic(dataset, imgsz=imgsz, p=hyp.mosaic)
     affine = RandomPerspective(degrees=hyp.degrees, translate=hyp.translate, scale=hyp.scale, shear=hyp.shear,
-                               perspective=hyp.perspective, pre_transform=None if stretch else "LetterBox")
+                               perspective=hyp.perspective,
+                               pre_transform=None if stretch else LetterBox(new_shape=(imgsz, imgsz)))
     pre_transform = Compose([mosaic, affine])
     if hyp.copy_paste_mode == "flip":
         pre_transform.insert(1, CopyPaste(p=hyp.copy_paste, mode=hyp.copy_paste_mode))
@@ -395,6 +494,53 @@ def v8_transforms(dataset, imgsz, hyp, stretch=False):
         RandomFlip(direction="vertical", p=hyp.flipud),
         RandomFlip(direction="horizontal", p=hyp.fliplr, flip_idx=None),
     ])
+
+
+def build_transforms(dataset, imgsz, hyp, augment=True):
+    """YOLODataset.build_transforms (data/dataset.py:174-195) for detection: the training chain, or the validation
+    LetterBox(scaleup=False), followed by Format."""
+    if augment:
+        rect = getattr(dataset, "rect", False)
+        hyp.mosaic = hyp.mosaic if augment and not rect else 0.0
+        hyp.mixup = hyp.mixup if augment and not rect else 0.0
+        transforms = v8_transforms(dataset, imgsz, hyp)
+    else:
+        transforms = Compose([LetterBox(new_shape=(imgsz, imgsz), scaleup=False)])
+    transforms.append(Format(bbox_format="xywh", normalize=True, return_mask=getattr(dataset, "use_segments", False),
+                             return_keypoint=getattr(dataset, "use_keypoints", False),
+                             return_obb=getattr(dataset, "use_obb", False), batch_idx=True,
+                             mask_ratio=getattr(hyp, "mask_ratio", 4), mask_overlap=getattr(hyp, "overlap_mask", True),
+                             bgr=hyp.bgr if augment else 0.0))
+    return transforms
+
+
+def close_mosaic(dataset, hyp):
+    """YOLODataset.close_mosaic (data/dataset.py:197-202; the trainer calls it for the last `close_mosaic` epochs,
+    engine/trainer.py:749-751): mosaic, copy_paste and mixup off, dataset.transforms rebuilt."""
+    hyp.mosaic = 0.0
+    hyp.copy_paste = 0.0
+    hyp.mixup = 0.0
+    dataset.transforms = build_transforms(dataset, dataset.imgsz, hyp, getattr(dataset, "augment", True))
+    return dataset.transforms
+
+
+def resize_linear_tables(s, n):
+    """cv::resize's 8-bit INTER_LINEAR coefficients of one axis, source length s -> n (imgproc/resize.cpp, restated:
+    PARITY UNPINNED against real OpenCV): scale = 1 / (n / s) in double, f = (float)((d + 0.5) * scale - 0.5),
+    i = floor(f), f -= i; i < 0 -> (0, 0), i >= s - 1 -> (s - 1, 0); (short)cvRound((1.f - f) * 2048) and
+    (short)cvRound(f * 2048) (INTER_RESIZE_COEF_BITS 11, round half to even). Returns (i, c0, c1) int32 arrays."""
+    scale = 1.0 / (n / s)
+    f = ((np.arange(n, dtype=np.float64) + 0.5) * scale - 0.5).astype(np.float32)
+    i = np.floor(f).astype(np.int64)
+    f = f - i.astype(np.float32)
+    lo, hi = i < 0, i >= s - 1
+    f[lo | hi] = 0
+    i[lo] = 0
+    i[hi] = s - 1
+    one, coef = np.float32(1.0), np.float32(2048.0)
+    c0 = np.clip(np.rint((one - f) * coef), -32768, 32767)
+    c1 = np.clip(np.rint(f * coef), -32768, 32767)
+    return i.astype(np.int32), c0.astype(np.int32), c1.astype(np.int32)
 
 
 def warp_affine_tables(M, dsize):
@@ -440,6 +586,8 @@ def render(plans, device="cuda", out=None):
     W, H = plans[0].size
     if any(p.size != (W, H) for p in plans):
         raise ValueError("render: every image of a batch must have the same size")
+    if any(p.resize is not None for p in plans):
+        raise ValueError("render: a LetterBox resize is rendered by render_letterbox (adr_letterbox_u8)")
     srcs, index = [], {}
     descs = (AugDesc * B)()
     tabs, luts = [], []
@@ -484,9 +632,120 @@ def render(plans, device="cuda", out=None):
     return out
 
 
+class LetterboxDesc(ctypes.Structure):
+    """adr_letterbox_desc (include/adr.h)."""
+    _fields_ = [("off", ctypes.c_int64)] + [(n, ctypes.c_int) for n in (
+        "sw", "sh", "nw", "nh", "left", "top", "mode", "tab_off", "rgb", "pad_")]
+
+
+LB_COPY, LB_LINEAR, LB_AREA2 = 0, 1, 2
+
+
+def _letterbox_geometry(p):
+    """(src, nw, nh, left, top) of a plan adr_letterbox_u8 can render; src None: nothing but the 114 fill."""
+    if p.M is not None or p.lut is not None or p.flip_ud or p.flip_lr or len(p.tiles) > 1:
+        raise ValueError("render_letterbox: the plan has mosaic / warp / HSV / flip stages (render() takes those)")
+    if not p.tiles:
+        return None, 0, 0, 0, 0
+    src, x1a, y1a, x2a, y2a, x1b, y1b = p.tiles[0]
+    sh, sw = src.shape[:2]
+    if (x1b, y1b, x2a - x1a, y2a - y1a) != (0, 0, sw, sh):
+        raise ValueError("render_letterbox: the plan's tile is not one whole source image")
+    if p.resize is not None:
+        return (src,) + tuple(p.resize)
+    return src, sw, sh, x1a, y1a  # pad only
+
+
+def render_letterbox(plans_or_images, new_shape=None, device="cuda", out=None, rgb=True, **letterbox_args):
+    """Run adr_letterbox_u8 for a list of letterbox ImagePlans and / or HWC BGR uint8 images (letterboxed here with
+    LetterBox(new_shape, **letterbox_args), planes in RGB order when `rgb`; a plan keeps its own channel order).
+    Returns (uint8 (B, 3, H, W) batch, [((ratio_w, ratio_h), (left, top)) per image]). `out`: an existing uint8
+    (B', 3, H, W) device tensor, B' >= the number of images, written in place; the slots beyond the images are
+    filled with 114."""
+    from ..native import lib
+    from ..kernels import stream
+
+    if ctypes.sizeof(LetterboxDesc) != lib.adr_letterbox_desc_size():
+        raise RuntimeError("adr_letterbox_desc layout mismatch between adrefine and libadr_hip")
+    plans, lb = [], None
+    for im in plans_or_images:
+        if not isinstance(im, ImagePlan):
+            if new_shape is None:
+                raise ValueError("render_letterbox: images need new_shape")
+            lb = lb or LetterBox(new_shape, **letterbox_args)
+            im = lb(image=im)
+            im.rgb = bool(rgb)
+        plans.append(im)
+    if not plans:
+        raise ValueError("render_letterbox: no images")
+    W, H = plans[0].size
+    if any(p.size != (W, H) for p in plans):
+        raise ValueError("render_letterbox: every image of a batch must have the same letterboxed size")
+    if out is not None:
+        if out.dtype != torch.uint8 or not out.is_contiguous() or tuple(out.shape[1:]) != (3, H, W) \
+                or out.shape[0] < len(plans):
+            raise ValueError(f"render_letterbox: out {tuple(out.shape)} does not take {len(plans)} images of "
+                             f"(3, {H}, {W}) uint8")
+        device = out.device
+    B = len(plans) if out is None else out.shape[0]
+    descs = (LetterboxDesc * B)()
+    srcs, index, tabs, info = [], {}, [], []
+    off = ntab = 0
+    for b, p in enumerate(plans):
+        src, nw, nh, left, top = _letterbox_geometry(p)
+        info.append(p.ratio_pad if p.ratio_pad is not None else ((1.0, 1.0), (left, top)))
+        d = descs[b]
+        if src is None:
+            continue  # nw == 0: fill
+        if nw > W - left or nh > H - top or left < 0 or top < 0:
+            raise ValueError(f"render_letterbox: image {b} ({nw} x {nh} at {left}, {top}) outside {W} x {H}")
+        key = id(src)
+        if key not in index:
+            index[key] = off
+            srcs.append(np.ascontiguousarray(src).reshape(-1))
+            off += src.size
+        sh, sw = src.shape[:2]
+        d.off, d.sw, d.sh, d.nw, d.nh, d.left, d.top, d.rgb = index[key], sw, sh, nw, nh, left, top, int(p.rgb)
+        if (sw, sh) == (nw, nh):
+            d.mode = LB_COPY
+        elif (sw, sh) == (2 * nw, 2 * nh):
+            d.mode = LB_AREA2  # cv::resize: INTER_LINEAR with an exact 2x shrink takes the INTER_AREA fast path
+        else:
+            d.mode, d.tab_off = LB_LINEAR, ntab
+            tab = np.concatenate(resize_linear_tables(sw, nw) + resize_linear_tables(sh, nh))
+            tabs.append(tab)
+            ntab += tab.size
+    pool_np = np.concatenate(srcs) if srcs else np.zeros(1, np.uint8)
+    pool = torch.from_numpy(pool_np).to(device, non_blocking=True)
+    dd = torch.frombuffer(bytearray(descs), dtype=torch.uint8).to(device, non_blocking=True)
+    tb = torch.from_numpy(np.concatenate(tabs) if tabs else np.zeros(1, np.int32)).to(device, non_blocking=True)
+    if out is None:
+        out = torch.empty(B, 3, H, W, dtype=torch.uint8, device=device)
+    lib.adr_letterbox_u8(ctypes.c_void_p(pool.data_ptr()), pool_np.size, ctypes.c_void_p(dd.data_ptr()),
+                         ctypes.cast(descs, ctypes.c_void_p), B, ctypes.c_void_p(tb.data_ptr()), ntab,
+                         ctypes.c_void_p(out.data_ptr()), H, W, stream())
+    out._adr_keep = (pool, dd, tb)  # the inputs live until the launch has read them (stream order)
+    return out, info
+
+
 def collate_fn(batch, device="cuda"):
-    """YOLODataset.collate_fn (data/dataset.py:230-246) with the images rendered on the GPU in one launch."""
-    new = {"img": render([b["img"] for b in batch], device)}
+    """YOLODataset.collate_fn (data/dataset.py:230-246) with the images rendered on the GPU: one launch of
+    adr_augment_u8, or of adr_letterbox_u8 for plans whose LetterBox resizes (one of each for a mixed batch)."""
+    plans = [b["img"] for b in batch]
+    lb = [i for i, p in enumerate(plans) if p.resize is not None]
+    if not lb:
+        img = render(plans, device)
+    elif len(lb) == len(plans):
+        img = render_letterbox(plans, device=device)[0]
+    else:
+        rest = [i for i in range(len(plans)) if plans[i].resize is None]
+        if any(p.size != plans[0].size for p in plans):
+            raise ValueError("collate_fn: every image of a batch must have the same size")
+        W, H = plans[0].size
+        img = torch.empty(len(plans), 3, H, W, dtype=torch.uint8, device=device)
+        img[lb] = render_letterbox([plans[i] for i in lb], device=device)[0]
+        img[rest] = render([plans[i] for i in rest], device)
+    new = {"img": img}
     for k in ("cls", "bboxes"):
         new[k] = torch.cat([b[k] for b in batch], 0)
     new["batch_idx"] = torch.cat([b["batch_idx"] + i for i, b in enumerate(batch)], 0)

@@ -5,9 +5,10 @@ models/yolo/detect/val.py:82-99 the validator's NMS call).
 One batch = the dataloader's uint8 NCHW images -> /255 (fused into the stem kernel, detect/train.py:57-59's
 preprocess) -> eval forward (BatchNorm with running statistics) -> DFL decode (adr_detect_decode) ->
 non_max_suppression (adr_nms). After one eager warm-up the whole chain is captured into a single hipGraph, so a
-batch is one graph launch plus (for `predict`) one host read of the per-image detection counts. Letterboxing
-and scale_boxes back to the source image are host-side image handling outside this path; callers feed
-network-sized batches.
+batch is one graph launch plus (for `predict`) one host read of the per-image detection counts. `predict`,
+`run_padded` and `capture` take network-sized uint8 batches; `predict_images` takes raw source images of any
+sizes: it letterboxes them on the device (adr_letterbox_u8, straight into the graph's input) and maps the
+detections back to each source image (adr_scale_boxes).
 """
 from __future__ import annotations
 
@@ -79,5 +80,46 @@ class FusedPredictor:
         counts = n.tolist()
         check_counts(counts, out.device)
         return [out[i, :k].clone() for i, k in enumerate(counts)]
+
+    def predict_images(self, imgs, imgsz=None):
+        """The reference's predict on raw images (engine/predictor.py:125, 144-156 letterbox + BGR -> RGB + CHW;
+        models/yolo/detect/predict.py postprocess with ops.scale_boxes): `imgs` is a list of HWC BGR uint8 numpy
+        images of any sizes; returns the list of (n_i, 6) tensors in each source image's own coordinates.
+
+        With a captured graph, 1 <= len(imgs) <= B of the captured batch: every image is letterboxed (auto=False) to
+        the captured (H, W) by adr_letterbox_u8 directly into the graph's static input (unused slots are filled with
+        114 and their outputs dropped), the graph is replayed, adr_scale_boxes maps the padded output back in place
+        and the per-image counts are the one host read. Without a graph the batch runs eagerly at `imgsz` (int or
+        (h, w)). The reference's auto=True minimum rectangle for batches of same-shape images is not used: the
+        shapes are fixed by the graph."""
+        from ..data.augment import render_letterbox
+        from ..kernels import fptr, stream
+        from ..native import lib
+        from ..utils.ops import scale_boxes_table, scale_gain_pad
+        imgs = list(imgs)
+        if self.graph is not None and imgsz is None:
+            B, _, H, W = self.static_in.shape
+            if not 1 <= len(imgs) <= B:
+                raise ValueError(f"predict_images: {len(imgs)} images for a graph captured at batch {B}")
+            batch, _ = render_letterbox(imgs, (H, W), out=self.static_in, rgb=True, auto=False)
+        else:
+            if imgsz is None:
+                raise ValueError("predict_images: without a captured graph pass imgsz")
+            H, W = (imgsz, imgsz) if isinstance(imgsz, int) else imgsz
+            if not imgs:
+                raise ValueError("predict_images: no images")
+            dev = next(self.model.parameters()).device
+            batch, _ = render_letterbox(imgs, (H, W), device=dev, rgb=True, auto=False)
+        out, n = self.run_padded(batch)
+        rows = []
+        for i in range(out.shape[0]):
+            h0, w0 = imgs[i].shape[:2] if i < len(imgs) else (H, W)
+            gain, pad = scale_gain_pad((H, W), (h0, w0))
+            rows.append((gain, pad[0], pad[1], w0, h0))
+        tab = scale_boxes_table(rows, out.device)
+        lib.adr_scale_boxes(fptr(out), fptr(n), fptr(tab), out.shape[0], out.shape[1], out.shape[2], 0, stream())
+        counts = n.tolist()
+        check_counts(counts, out.device)
+        return [out[i, :counts[i]].clone() for i in range(len(imgs))]
 
     __call__ = predict

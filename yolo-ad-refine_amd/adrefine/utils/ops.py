@@ -84,6 +84,74 @@ def non_max_suppression(prediction, conf_thres=0.25, iou_thres=0.45, classes=Non
     return [out[i, :k] for i, k in enumerate(counts)]
 
 
+def scale_gain_pad(img1_shape, img0_shape, ratio_pad=None):
+    """The host half of scale_boxes (ops.py:106-114): gain = old / new and the (x, y) padding, in Python floats."""
+    if ratio_pad is None:  # calculate from img0_shape
+        gain = min(img1_shape[0] / img0_shape[0], img1_shape[1] / img0_shape[1])
+        pad = (round((img1_shape[1] - img0_shape[1] * gain) / 2 - 0.1),
+               round((img1_shape[0] - img0_shape[0] * gain) / 2 - 0.1))
+    else:
+        gain = ratio_pad[0][0]
+        pad = ratio_pad[1]
+    return gain, pad
+
+
+def scale_boxes_table(rows, device):
+    """Device table of adr_scale_boxes: one fp32 row {gain, padx, pady, w0, h0} per image."""
+    return torch.tensor(rows, dtype=torch.float32).reshape(-1, 5).to(device)
+
+
+def _scale_boxes_device(boxes, row, xywh=False):
+    """adr_scale_boxes on one image's boxes (..., >= 4) fp32, in place (a row-strided view such as pred[:, :4] too)."""
+    if boxes.dtype != torch.float32 or boxes.shape[-1] < 4:
+        raise RuntimeError("scale_boxes / clip_boxes on a device tensor take fp32 boxes (..., >= 4)")
+    if boxes.numel() == 0:
+        return boxes
+    if boxes.is_contiguous():
+        rows, cols = boxes.numel() // boxes.shape[-1], boxes.shape[-1]
+    elif boxes.dim() == 2 and boxes.stride(1) == 1 and boxes.stride(0) >= boxes.shape[1]:
+        rows, cols = boxes.shape[0], boxes.stride(0)
+    else:
+        raise RuntimeError("scale_boxes / clip_boxes on a device tensor take contiguous boxes or a 2-D row view")
+    tab = scale_boxes_table([row], boxes.device)
+    lib.adr_scale_boxes(fptr(boxes), None, fptr(tab), 1, rows, cols, int(bool(xywh)), stream())
+    return boxes
+
+
+def clip_boxes(boxes, shape):
+    """ops.py:315-334: clip boxes (x1, y1, x2, y2, ...) to shape (height, width), in place."""
+    if isinstance(boxes, torch.Tensor):
+        if boxes.is_cuda:
+            return _scale_boxes_device(boxes, (1.0, 0, 0, shape[1], shape[0]))  # (x - 0) / 1: the clamp alone
+        boxes[..., 0] = boxes[..., 0].clamp(0, shape[1])  # x1
+        boxes[..., 1] = boxes[..., 1].clamp(0, shape[0])  # y1
+        boxes[..., 2] = boxes[..., 2].clamp(0, shape[1])  # x2
+        boxes[..., 3] = boxes[..., 3].clamp(0, shape[0])  # y2
+    else:  # np.array
+        boxes[..., [0, 2]] = boxes[..., [0, 2]].clip(0, shape[1])  # x1, x2
+        boxes[..., [1, 3]] = boxes[..., [1, 3]].clip(0, shape[0])  # y1, y2
+    return boxes
+
+
+def scale_boxes(img1_shape, boxes, img0_shape, ratio_pad=None, padding=True, xywh=False):
+    """ops.py:88-123: rescale boxes from img1_shape (the letterboxed network input) to img0_shape (the source image),
+    in place. Gain and pad on the host as the reference computes them; device tensors go through adr_scale_boxes
+    (subtract, a true fp32 division, clamp: the bits of the reference's torch arithmetic), CPU tensors through the
+    reference's torch arithmetic."""
+    gain, pad = scale_gain_pad(img1_shape, img0_shape, ratio_pad)
+    if isinstance(boxes, torch.Tensor) and boxes.is_cuda:
+        px, py = (pad[0], pad[1]) if padding else (0, 0)
+        return _scale_boxes_device(boxes, (gain, px, py, img0_shape[1], img0_shape[0]), xywh)
+    if padding:
+        boxes[..., 0] -= pad[0]  # x padding
+        boxes[..., 1] -= pad[1]  # y padding
+        if not xywh:
+            boxes[..., 2] -= pad[0]  # x padding
+            boxes[..., 3] -= pad[1]  # y padding
+    boxes[..., :4] /= gain
+    return clip_boxes(boxes, img0_shape)
+
+
 def check_counts(counts, device):
     """A negative per-image count is adr_nms's report of a grid-barrier timeout (the persistent kernel's phases ran
     out of order). Raise, after returning the workspace to its first-use state IN PLACE (adr_nms_reset zeroes the
