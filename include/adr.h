@@ -766,6 +766,35 @@ int adr_nms(const float* y, int B, int nc, int A, float conf, float iou, int mul
  * stays valid. */
 int adr_nms_reset(void* ws, size_t ws_bytes, void* stream);
 
+/* ---------------------------------------------------------------------------------------------------------
+ * Detection validator, everything update_metrics does per image after NMS (models/yolo/detect/val.py:104-161,
+ * ConfusionMatrix.process_batch utils/metrics.py:932-989) for a whole batch in one launch, one workgroup per image.
+ * det (B, rows, 6) fp32: the padded adr_nms output ALREADY in native image space (run adr_scale_boxes first), rows
+ * <= 300; counts[B]. Labels as collate_fn delivers them, sorted by image: cls[N], normalised xywh bboxes[N,4];
+ * gt_off[B+1] int32 CSR offsets in device memory and gt_off_host, the same offsets in host memory, which are
+ * validated before the launch (start 0, monotone, end N). table: adr_scale_boxes' rows {gain, padx, pady, w0, h0};
+ * H, W the network input size; thr[T] fp32 IoU thresholds, T <= 16; nc <= 1024.
+ *   gt_xyxy[N,4]        labels in native space: xywh2xyxy, * (W, H, W, H), (v - pad) / gain (IEEE fp32 division),
+ *                       clip to (w0, h0) - the reference's fp32 arithmetic in its order
+ *   correct (B,rows,T)  uint8, adr_match_predictions' rule on IoUs computed on the fly (adr_box_iou's operation
+ *                       order, eps 1e-7): a detection's best same-class label, exact IoU ties to the larger label
+ *                       index; a label is credited at thr[t] to the lowest-index detection whose best it is with
+ *                       IoU >= thr[t]. Rows >= counts[b] are written 0.
+ *   cm (nc+1,nc+1)      int32, ACCUMULATED; NULL skips it. Detections with conf > cm_conf, class-agnostic pairs with
+ *                       IoU > cm_iou; each detection keeps its highest-IoU pair, each label then its highest-IoU
+ *                       surviving pair. Matched label: [det_cls, gt_cls] += 1; unmatched label: [nc, gt_cls] += 1;
+ *                       kept detection without a match: [det_cls, nc] += 1 only if the image has a match (the
+ *                       reference's `if n:`). An image without labels adds nothing (the validator's call pattern,
+ *                       val.py:140-159). Exact IoU ties between candidate pairs are decided by numpy's unstable sort
+ *                       in the reference - PARITY UNPINNED; here a detection takes the larger label index and a
+ *                       label the lower detection index. Class ids used as indices are clamped to [0, nc].
+ *   nt_per_class[nc]    int32, ACCUMULATED: labels per class; nt_per_image[nc]: images with >= 1 label of the class.
+ * Accumulation is by integer atomics (order-free, deterministic). */
+int adr_val_match(const float* det, const int* counts, int B, int rows, const float* cls, const float* bboxes,
+                  const int* gt_off, const int* gt_off_host, int N, const float* table, int H, int W,
+                  const float* thr, int T, float cm_conf, float cm_iou, int nc, float* gt_xyxy,
+                  unsigned char* correct, int* cm, int* nt_per_class, int* nt_per_image, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

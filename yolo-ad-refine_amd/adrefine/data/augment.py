@@ -749,4 +749,9 @@ def collate_fn(batch, device="cuda"):
     for k in ("cls", "bboxes"):
         new[k] = torch.cat([b[k] for b in batch], 0)
     new["batch_idx"] = torch.cat([b["batch_idx"] + i for i, b in enumerate(batch)], 0)
+    # per-image metadata the validator needs (scale_boxes back to the source image), as per-image lists like the
+    # reference's collate of non-tensor values; only when every sample carries the key
+    for k in ("im_file", "ori_shape", "resized_shape", "ratio_pad"):
+        if all(k in b for b in batch):
+            new[k] = [b[k] for b in batch]
     return new

@@ -93,6 +93,24 @@ def save_checkpoint(trainer, path, epoch, best_fitness=None, train_args=None, tr
     Path(path).write_bytes(buf.getvalue())
 
 
+def save_last_and_best(trainer, wdir, epoch, fitness, best_fitness=None, **kw):
+    """The model-selection half of save_model (trainer.py:437-446, 507-540): always writes wdir/last.pt, and the
+    same bytes to wdir/best.pt when this epoch's fitness is the best so far — `fitness >= best_fitness`, the
+    reference's comparison (trainer.py:538, an equal fitness replaces best.pt). The running best (including this
+    epoch) is stored in the file and returned; pass it back in at the next epoch. best_fitness None (a fresh run,
+    or resume()'s 0.0 or None of a checkpoint without one) makes the first epoch the best. kw: save_checkpoint's
+    train_args / train_metrics / train_results."""
+    wdir = Path(wdir)
+    wdir.mkdir(parents=True, exist_ok=True)
+    fitness = float(fitness)
+    is_best = best_fitness is None or fitness >= best_fitness
+    best = fitness if best_fitness is None else max(float(best_fitness), fitness)
+    save_checkpoint(trainer, wdir / "last.pt", epoch, best_fitness=best, **kw)
+    if is_best:
+        (wdir / "best.pt").write_bytes((wdir / "last.pt").read_bytes())
+    return best
+
+
 def load_checkpoint(path):
     """torch.load with weights_only=True (nothing in the file executes)."""
     return torch.load(path, map_location="cpu", weights_only=True)

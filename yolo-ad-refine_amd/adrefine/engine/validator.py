@@ -1,0 +1,84 @@
+"""Detection validator — the reference's models/yolo/detect/val.py DetectionValidator on the device
+(engine/validator.py:104-216 the loop, val.py:92-161 postprocess + update_metrics, :179-187 get_stats).
+
+Per batch: the collated uint8 images go through a FusedPredictor (forward + decode + NMS with the validator's
+settings, one hipGraph after the first batch), then adr_scale_boxes maps the padded detections to each source image
+and adr_val_match does all per-image bookkeeping in one launch (labels to native space, TP matching at the ten IoU
+thresholds, confusion matrix, label tallies). Nothing is read back inside the loop: the statistics stay on the
+device until the AP integration at the end (utils/metrics.DetectionStats.results).
+
+Differences from the reference, by design: one hipGraph holds the forward, the decode and the NMS, so
+speed['inference'] covers all three and speed['postprocess'] is the scaling + matching (the reference counts NMS as
+postprocess); single_cls on a model with more than one class needs agnostic multi-label NMS, which adr_nms does not
+provide (the predictor raises NotImplementedError) — a single_cls run evaluates a one-class model, as the
+reference's single_cls dataset yields; no json / txt export and no plots.
+"""
+from __future__ import annotations
+
+import torch
+
+from ..utils.metrics import DetectionStats
+from .predictor import FusedPredictor
+
+RESULT_KEYS = ("metrics/precision(B)", "metrics/recall(B)", "metrics/mAP50(B)", "metrics/mAP50-95(B)", "fitness")
+
+
+class DetectionValidator:
+    """validator = DetectionValidator(model, nc); results = validator(batches).
+
+    batches: an iterable of collated validation batches (data/augment.collate_fn on the val LetterBox + Format
+    chain): `img` uint8 (B, 3, H, W), `cls`, `bboxes` (normalised xywh), `batch_idx` (host tensors), and the
+    per-image lists `ori_shape` and `ratio_pad`. The first batch's shape is captured; a smaller last batch runs
+    eagerly. Returns the reference's results_dict keys plus 'fitness', the per-class arrays and tallies of
+    DetectionStats.results() ('p', 'r', 'ap', 'ap_class_index', 'nt_per_class', 'nt_per_image', 'seen',
+    'confusion_matrix') and 'speed' = {'preprocess', 'inference', 'postprocess'} in ms per image from HIP events
+    read after the loop.
+
+    `model` is the validator's own copy of the network (eval mode; load_ema overwrites its weights)."""
+
+    def __init__(self, model, nc, conf=0.001, iou=0.7, max_det=300, agnostic=False, single_cls=False, cm_conf=None):
+        self.model, self.nc = model, nc
+        self.single_cls = bool(single_cls)
+        # val.py:94-102: multi_label=True, agnostic = single_cls or agnostic_nms
+        self.predictor = FusedPredictor(model, conf=conf, iou=iou, max_det=max_det,
+                                        agnostic=bool(agnostic or single_cls), multi_label=True)
+        self.cm_conf = conf if cm_conf is None else cm_conf  # val.py:83 ConfusionMatrix(conf=args.conf)
+        self.stats = None
+
+    def load_ema(self, trainer):
+        """Evaluate the trainer's EMA weights (the reference validates self.ema.ema, engine/trainer.py:437):
+        floating entries from trainer.ema_state_dict(), integer buffers from trainer.ema_int, then the predictor's
+        packed operands and eval BatchNorm coefficients are refreshed (a captured graph stays valid)."""
+        ema = trainer.ema_state_dict()
+        with torch.no_grad():
+            for k, v in self.model.state_dict().items():
+                src = ema.get(k) if v.dtype.is_floating_point else trainer.ema_int.get(k)
+                if src is None:
+                    raise KeyError(f"load_ema: the trainer's EMA has no entry {k}")
+                v.copy_(src.to(v.device))
+        self.predictor.sync_weights()
+
+    def __call__(self, batches):
+        dev = next(self.model.parameters()).device
+        self.stats = stats = DetectionStats(self.nc)
+        events = []
+        for batch in batches:
+            img = batch["img"]
+            if self.predictor.graph is None:
+                self.predictor.capture(img.to(dev))
+            e = [torch.cuda.Event(enable_timing=True) for _ in range(4)]
+            e[0].record()
+            img = img.to(dev, non_blocking=True)
+            e[1].record()
+            out, n = self.predictor.run_padded(img)
+            e[2].record()
+            stats.update_batched(out, n, batch, imgsz=img.shape[2:], cm_conf=self.cm_conf,
+                                 single_cls=self.single_cls)
+            e[3].record()
+            events.append((e, img.shape[0]))
+        res = stats.results()
+        torch.cuda.synchronize(dev)
+        seen = max(sum(b for _, b in events), 1)
+        ms = [sum(e[i].elapsed_time(e[i + 1]) for e, _ in events) / seen for i in range(3)]
+        res["speed"] = dict(zip(("preprocess", "inference", "postprocess"), ms))
+        return res
