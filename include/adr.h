@@ -567,6 +567,24 @@ int adr_augment_desc_size(void);
 int adr_letterbox_u8(const void* pool, size_t pool_bytes, const void* descs, const void* descs_host, int B,
                      const int* tables, int ntab, void* out, int H, int W, void* stream);
 int adr_letterbox_desc_size(void);
+/* BaseDataset.load_image's resize (data/base.py:168-172): cv2.resize(im, (nw, nh), INTER_LINEAR) for B images of
+ * different sizes in one launch, HWC BGR uint8 -> HWC BGR uint8, from a staging buffer (src, src_bytes long; sources
+ * at any byte offset, row stride sw * 3) into the resident image pool (dst, dst_bytes long, 4-byte aligned;
+ * destinations compact, row stride nw * 3) that adr_augment_u8 / adr_letterbox_u8 then read as their `pool`
+ * (adrefine/data/pool.py). descs: B device adr_resize_desc records {int64 src_off, dst_off; int sw, sh, nw, nh, mode,
+ * tab_off; size adr_resize_desc_size()} and descs_host the same records in host memory. mode and tables (ntab ints)
+ * are adr_letterbox_u8's: 0 copy (sw == nw, sh == nh), 1 linear (at tab_off: sx[nw], a0[nw], a1[nw], sy[nh], b0[nh],
+ * b1[nh]), 2 the 2 x 2 average (sw == 2 nw, sh == 2 nh); the per-sample arithmetic is one pair of device functions
+ * (csrc/adr_resize_sample.h) that both kernels call, integer only, PARITY UNPINNED against real OpenCV as there.
+ * prefix: B device ints, prefix[b] = sum over the images before b of ceil(ceil(nh * nw * 3 / 4) / 256): the first
+ * block of image b in the flattened grid (one thread per aligned destination dword, the last 1-3 bytes of an image
+ * as bytes; nothing outside a destination is written, whatever prefix holds). Validated on the host copy before
+ * the launch: sizes > 0, mode against the sizes, sources inside src_bytes, destinations inside dst_bytes and at
+ * multiples of 4, tables inside ntab, and no two destinations of the launch overlapping; any violation returns a
+ * non-zero status and launches nothing. */
+int adr_resize_u8(const void* src, size_t src_bytes, const void* descs, const void* descs_host, const int* prefix,
+                  int B, const int* tables, int ntab, void* dst, size_t dst_bytes, void* stream);
+int adr_resize_desc_size(void);
 /* ops.scale_boxes + clip_boxes (utils/ops.py:88-123, 315-334) in place on boxes (B, rows, cols >= 4) fp32, e.g. the
  * padded NMS output (B, max_det, 6): for the first four columns x = (x - pad) / gain (a true IEEE fp32 division,
  * as torch's `boxes /= gain`), then clamped to [0, w0] / [0, h0]. table: B device rows {gain, padx, pady, w0, h0}

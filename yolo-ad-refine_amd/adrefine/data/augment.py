@@ -21,7 +21,9 @@ the rest of the chain; a LetterBox that resizes is rendered by adr_letterbox_u8 
 INTER_LINEAR in OpenCV's fixed point + constant border + RGB / CHW). Not covered (raise): a LetterBox resize followed
 by warp / HSV / flip in one plan (cannot arise from a dataset), warpPerspective, MixUp or CopyPaste with p > 0,
 mosaic9, segments / keypoints. Source images come in resized as BaseDataset.load_image leaves them
-(data/base.py:151-190); decoding and that resize stay on the host."""
+(data/base.py:151-190): host arrays (uploaded with the batch), or DeviceImages of one data/pool.py DevicePool,
+decoded on the host once, resized by adr_resize_u8 and resident in HBM (data/dataset.py YOLODataset): then a batch
+uploads descriptors and tables only."""
 from __future__ import annotations
 
 import copy
@@ -92,8 +94,36 @@ class ImagePlan:
         return q
 
 
+def _is_device(src):
+    """A source image resident in a DevicePool (data/pool.py DeviceImage) instead of a host array."""
+    return hasattr(src, "pool") and hasattr(src, "off")
+
+
 def _plan(img):
-    return img if isinstance(img, ImagePlan) else ImagePlan(np.ascontiguousarray(img))
+    if isinstance(img, ImagePlan):
+        return img
+    return ImagePlan(img if _is_device(img) else np.ascontiguousarray(img))
+
+
+def _source_pool(plans, what):
+    """The DevicePool every tile source of the batch lives in, or None when all of them are host arrays."""
+    srcs = [t[0] for p in plans for t in p.tiles]
+    dev = [s for s in srcs if _is_device(s)]
+    if not dev:
+        return None
+    if len(dev) != len(srcs):
+        raise ValueError(f"{what}: the batch mixes host and device-resident source images")
+    pool = dev[0].pool
+    if any(s.pool is not pool for s in dev):
+        raise ValueError(f"{what}: the batch's device-resident source images come from two pools")
+    if any(s.off is None for s in dev):
+        raise ValueError(f"{what}: a source image was released from its pool")
+    return pool
+
+
+def _same_device(a, b):
+    """torch.device("cuda") names the current device: equal to any index of its type."""
+    return a.type == b.type and (a.index is None or b.index is None or a.index == b.index)
 
 
 class Compose:
@@ -588,6 +618,12 @@ def render(plans, device="cuda", out=None):
         raise ValueError("render: every image of a batch must have the same size")
     if any(p.resize is not None for p in plans):
         raise ValueError("render: a LetterBox resize is rendered by render_letterbox (adr_letterbox_u8)")
+    resident = _source_pool(plans, "render")  # sources already in HBM: no pixels are uploaded
+    if resident is not None:
+        if out is not None and not _same_device(out.device, resident.device):
+            raise ValueError("render: out is not on the device of the source images' pool")
+        resident.flush()
+        device = resident.device
     srcs, index = [], {}
     descs = (AugDesc * B)()
     tabs, luts = [], []
@@ -600,9 +636,12 @@ def render(plans, device="cuda", out=None):
         for k, (src, x1a, y1a, x2a, y2a, x1b, y1b) in enumerate(p.tiles):
             key = id(src)
             if key not in index:
-                index[key] = off
-                srcs.append(np.ascontiguousarray(src).reshape(-1))
-                off += src.size
+                if resident is not None:
+                    index[key] = src.off
+                else:
+                    index[key] = off
+                    srcs.append(np.ascontiguousarray(src).reshape(-1))
+                    off += src.size
             t = d.tile[k]
             t.off, t.sw = index[key], src.shape[1]
             t.x1a, t.y1a, t.x2a, t.y2a, t.x1b, t.y1b = x1a, y1a, x2a, y2a, x1b, y1b
@@ -619,7 +658,10 @@ def render(plans, device="cuda", out=None):
         if p.lut is not None:
             luts.append(p.lut.reshape(-1))
         d.flip_ud, d.flip_lr, d.rgb = int(p.flip_ud), int(p.flip_lr), int(p.rgb)
-    pool = torch.from_numpy(np.concatenate(srcs)).to(device, non_blocking=True)
+    if resident is not None:
+        pool = resident.tensor
+    else:
+        pool = torch.from_numpy(np.concatenate(srcs)).to(device, non_blocking=True)
     dd = torch.frombuffer(bytearray(descs), dtype=torch.uint8).to(device, non_blocking=True)
     tb = torch.from_numpy(np.concatenate(tabs) if tabs else np.zeros(1, np.int32)).to(device, non_blocking=True)
     lt = torch.from_numpy(np.concatenate(luts) if luts else np.zeros(1, np.uint8)).to(device, non_blocking=True)
@@ -687,6 +729,13 @@ def render_letterbox(plans_or_images, new_shape=None, device="cuda", out=None, r
             raise ValueError(f"render_letterbox: out {tuple(out.shape)} does not take {len(plans)} images of "
                              f"(3, {H}, {W}) uint8")
         device = out.device
+    resident = _source_pool(plans, "render_letterbox")  # sources already in HBM: no pixels are uploaded
+    if resident is not None:
+        resident.flush()
+        if out is None:
+            device = resident.device
+        elif not _same_device(out.device, resident.device):
+            raise ValueError("render_letterbox: out is not on the device of the source images' pool")
     B = len(plans) if out is None else out.shape[0]
     descs = (LetterboxDesc * B)()
     srcs, index, tabs, info = [], {}, [], []
@@ -701,9 +750,12 @@ def render_letterbox(plans_or_images, new_shape=None, device="cuda", out=None, r
             raise ValueError(f"render_letterbox: image {b} ({nw} x {nh} at {left}, {top}) outside {W} x {H}")
         key = id(src)
         if key not in index:
-            index[key] = off
-            srcs.append(np.ascontiguousarray(src).reshape(-1))
-            off += src.size
+            if resident is not None:
+                index[key] = src.off
+            else:
+                index[key] = off
+                srcs.append(np.ascontiguousarray(src).reshape(-1))
+                off += src.size
         sh, sw = src.shape[:2]
         d.off, d.sw, d.sh, d.nw, d.nh, d.left, d.top, d.rgb = index[key], sw, sh, nw, nh, left, top, int(p.rgb)
         if (sw, sh) == (nw, nh):
@@ -715,13 +767,16 @@ def render_letterbox(plans_or_images, new_shape=None, device="cuda", out=None, r
             tab = np.concatenate(resize_linear_tables(sw, nw) + resize_linear_tables(sh, nh))
             tabs.append(tab)
             ntab += tab.size
-    pool_np = np.concatenate(srcs) if srcs else np.zeros(1, np.uint8)
-    pool = torch.from_numpy(pool_np).to(device, non_blocking=True)
+    if resident is not None:
+        pool, pool_bytes = resident.tensor, resident.capacity
+    else:
+        pool_np = np.concatenate(srcs) if srcs else np.zeros(1, np.uint8)
+        pool, pool_bytes = torch.from_numpy(pool_np).to(device, non_blocking=True), pool_np.size
     dd = torch.frombuffer(bytearray(descs), dtype=torch.uint8).to(device, non_blocking=True)
     tb = torch.from_numpy(np.concatenate(tabs) if tabs else np.zeros(1, np.int32)).to(device, non_blocking=True)
     if out is None:
         out = torch.empty(B, 3, H, W, dtype=torch.uint8, device=device)
-    lib.adr_letterbox_u8(ctypes.c_void_p(pool.data_ptr()), pool_np.size, ctypes.c_void_p(dd.data_ptr()),
+    lib.adr_letterbox_u8(ctypes.c_void_p(pool.data_ptr()), pool_bytes, ctypes.c_void_p(dd.data_ptr()),
                          ctypes.cast(descs, ctypes.c_void_p), B, ctypes.c_void_p(tb.data_ptr()), ntab,
                          ctypes.c_void_p(out.data_ptr()), H, W, stream())
     out._adr_keep = (pool, dd, tb)  # the inputs live until the launch has read them (stream order)

@@ -21,6 +21,7 @@
 //
 // adr_scale_boxes: ops.scale_boxes (utils/ops.py:88-123) + clip_boxes (:315-334) in place on the padded NMS output.
 #include "adr_common.h"
+#include "adr_resize_sample.h"
 
 #include <cstdint>
 
@@ -28,7 +29,7 @@
 
 namespace adr {
 
-enum LbMode { LB_COPY = 0, LB_LINEAR = 1, LB_AREA2 = 2 };
+enum LbMode { LB_COPY = RS_COPY, LB_LINEAR = RS_LINEAR, LB_AREA2 = RS_AREA2 };  // adr_resize_sample.h
 
 struct LbDesc {
   long long off;   // byte offset of the source image (HWC BGR uint8) in the pool
@@ -43,9 +44,7 @@ struct LbDesc {
 
 namespace {
 
-__device__ __forceinline__ int clampi(int v, int lo, int hi) { return min(max(v, lo), hi); }
-
-// one output pixel (x, y) of image d as BGR
+// one output pixel (x, y) of image d as BGR; the resize arithmetic is adr_resize_sample.h's, shared with adr_resize_u8
 __device__ __forceinline__ void lb_pixel(const uint8_t* pool, const LbDesc& d, const int* tabs, int x, int y,
                                          int v[3]) {
   const int dx = x - d.left, dy = y - d.top;
@@ -53,37 +52,9 @@ __device__ __forceinline__ void lb_pixel(const uint8_t* pool, const LbDesc& d, c
     v[0] = v[1] = v[2] = 114;
     return;
   }
-  const uint8_t* S = pool + d.off;
-  const long pitch = (long)d.sw * 3;
-  if (d.mode == LB_LINEAR) {
-    const int* t = tabs + d.tab_off;
-    // table entries index the source; clamped so that a wrong table cannot read outside the image
-    const int sx0 = clampi(t[dx], 0, d.sw - 1), sx1 = min(sx0 + 1, d.sw - 1);
-    const int a0 = t[d.nw + dx], a1 = t[2 * d.nw + dx];
-    const int* u = t + 3 * d.nw;
-    const int sy0 = clampi(u[dy], 0, d.sh - 1), sy1 = min(sy0 + 1, d.sh - 1);
-    const int b0 = u[d.nh + dy], b1 = u[2 * d.nh + dy];
-    const uint8_t* r0 = S + sy0 * pitch;
-    const uint8_t* r1 = S + sy1 * pitch;
+  const ResizeTaps t = resize_taps(pool + d.off, d.sw, d.sh, d.nw, d.nh, d.mode, tabs + d.tab_off, dx, dy);
 #pragma unroll
-    for (int k = 0; k < 3; ++k) {
-      const int D0 = r0[sx0 * 3 + k] * a0 + r0[sx1 * 3 + k] * a1;
-      const int D1 = r1[sx0 * 3 + k] * a0 + r1[sx1 * 3 + k] * a1;
-      const int q = (((b0 * (D0 >> 4)) >> 16) + ((b1 * (D1 >> 4)) >> 16) + 2) >> 2;
-      v[k] = clampi(q, 0, 255);
-    }
-  } else if (d.mode == LB_AREA2) {
-    const int sx = min(2 * dx, d.sw - 2), sy = min(2 * dy, d.sh - 2);
-    const uint8_t* r0 = S + sy * pitch + sx * 3;
-    const uint8_t* r1 = r0 + pitch;
-#pragma unroll
-    for (int k = 0; k < 3; ++k) v[k] = (r0[k] + r0[3 + k] + r1[k] + r1[3 + k] + 2) >> 2;
-  } else {
-    const uint8_t* p = S + min(dy, d.sh - 1) * pitch + min(dx, d.sw - 1) * 3;
-    v[0] = p[0];
-    v[1] = p[1];
-    v[2] = p[2];
-  }
+  for (int k = 0; k < 3; ++k) v[k] = resize_sample(t, d.mode, k);
 }
 
 }  // namespace
