@@ -711,6 +711,21 @@ int adr_opt_entry_size(void);
 int adr_opt_chunk_size(void);
 int adr_opt_step(const void* tab, const void* chunks, int nchunks, float* partial, float max_norm,
                  const float* hyper, float* norm_out, void* stream);
+/* adr_opt_step_adam: the same tail with torch.optim.Adam / AdamW (single-tensor path, amsgrad off) in place of
+ * SGD: clip, then per element gv = g*coef; Adam: gv += wd*p, AdamW: p *= 1 - lr*wd; m += (gv - m)*(1 - beta1);
+ * v = v*beta2 + (1 - beta2)*gv*gv; p -= step_size * (m / (sqrt(v)/bc2_sqrt + eps)); g = 0; EMA as above. Every
+ * operation rounds once (no FMA contraction, IEEE sqrt and divide). The first moment m is the entry's
+ * momentum_buf; the second moment v lives sq_offset ELEMENTS after it (momentum_buf + sq_offset), so the tables
+ * keep their layout. hyper is DEVICE memory, 16 floats:
+ * [lr0, lr1, lr2, wd0, wd1, wd2, 1-beta1, beta2, 1-beta2, eps, step_size0, step_size1, step_size2, bc2_sqrt,
+ *  ema_decay, decoupled] with step_size_g = lr_g / (1 - beta1^t), bc2_sqrt = sqrt(1 - beta2^t) for the optimizer
+ * step t (1-based) being taken and decoupled != 0 for AdamW. Every scalar is computed by the caller in double
+ * and rounded once, as torch passes its Python floats to the fp32 ops: beta1 enters only as the lerp weight
+ * 1 - beta1, and 1 - beta2 cannot be recovered from the rounded beta2 (1.f - 0.999f is off by 5e-5 relative).
+ * The caller rewrites the vector (adr_set_f32) before every step, so a captured hipGraph follows both the
+ * schedule and the bias corrections. */
+int adr_opt_step_adam(const void* tab, const void* chunks, int nchunks, float* partial, float max_norm,
+                      const float* hyper, long sq_offset, float* norm_out, void* stream);
 /* dst[0..n) = vals[0..n) (host array, n <= 16) as a stream-ordered kernel (values travel as kernel
  * arguments: no host buffer lifetime to manage, safe to enqueue ahead of a graph replay). */
 int adr_set_f32(float* dst, const float* vals, int n, void* stream);

@@ -13,6 +13,10 @@ momentum buffers fp16 like utils/torch_utils.convert_optimizer_state_dict_to_fp1
 Resume follows resume_training: the model AND the EMA start from ckpt['ema'] (the reference resumes the model
 from the EMA weights of last.pt), momentum buffers from ckpt['optimizer'], EMA update count from
 ckpt['updates'], start_epoch = epoch + 1.
+
+An Adam / AdamW trainer (FusedTrainer(optimizer=...)) writes the torch.optim.Adam / AdamW state_dict instead
+('step' fp32, 'exp_avg' and 'exp_avg_sq' fp16, betas=(momentum, 0.999)) and resumes both moments and the step
+count from it; a checkpoint of the other optimizer family is refused with a ValueError.
 """
 from __future__ import annotations
 
@@ -38,8 +42,37 @@ def _ref_param_order(trainer):
     return [(n, 2) for n in by_group[2]] + [(n, 0) for n in by_group[0]] + [(n, 1) for n in by_group[1]]
 
 
+def _adam_state_dict(trainer):
+    """torch.optim.Adam / AdamW state_dict as build_optimizer creates the optimizer (trainer.py:795, 807-808:
+    betas=(momentum, 0.999), weight_decay 0.0 for g2 and g1, the decay on g0): per-parameter 'step' (fp32 scalar,
+    left alone by convert_optimizer_state_dict_to_fp16, utils/torch_utils.py:640-651), 'exp_avg' and 'exp_avg_sq'
+    in fp16. fp16 flushes exp_avg_sq below 2^-24 to zero, as the reference's own checkpoints do (DESIGN)."""
+    idx = {name: i for i, (name, _p, _g, isp) in enumerate(trainer.entries) if isp}
+    state, groups = {}, {2: [], 0: [], 1: []}
+    for k, (name, grp) in enumerate(_ref_param_order(trainer)):
+        ei = idx[name]
+        _, t, _, _ = trainer.entries[ei]
+        if trainer.opt_steps > 0 and getattr(t, "_adr_used", False):
+            sl = slice(trainer._goff[ei], trainer._goff[ei] + t.numel())
+            state[k] = {"step": torch.tensor(float(trainer.opt_steps)),
+                        "exp_avg": trainer.mom[sl].view(t.shape).detach().half().cpu(),
+                        "exp_avg_sq": trainer.sq[sl].view(t.shape).detach().half().cpu()}
+        groups[grp].append(k)
+    # the group keys of the installed torch's optimizer, so its load_state_dict accepts the file
+    cls = getattr(torch.optim, trainer.optimizer)
+    defaults = cls([torch.zeros(1)], lr=trainer.sched.lr0, betas=(trainer.momentum, trainer.beta2), eps=trainer.eps,
+                   weight_decay=0.0).defaults
+    wds = {0: trainer.wd, 1: 0.0, 2: 0.0}
+    pg = [{**defaults, "lr": trainer.lr[g], "weight_decay": wds[g], "initial_lr": trainer.sched.lr0,
+           "params": groups[g]} for g in (2, 0, 1)]
+    return {"state": state, "param_groups": pg}
+
+
 def optimizer_state_dict(trainer):
-    """torch.optim.SGD state_dict of the trainer's momentum buffers, reference grouping, fp16 buffers."""
+    """torch.optim.SGD state_dict of the trainer's momentum buffers (or, for an Adam / AdamW trainer, the
+    torch.optim.Adam / AdamW state_dict of both moments), reference grouping, fp16 buffers."""
+    if trainer.adam:
+        return _adam_state_dict(trainer)
     idx = {name: i for i, (name, _p, _g, isp) in enumerate(trainer.entries) if isp}
     state, groups = {}, {2: [], 0: [], 1: []}
     for k, (name, grp) in enumerate(_ref_param_order(trainer)):
@@ -121,6 +154,14 @@ def resume(trainer, ckpt):
     (start_epoch, best_fitness)."""
     start_epoch = ckpt.get("epoch", -1) + 1
     assert start_epoch > 0, "checkpoint marks training as finished"
+    opt = ckpt.get("optimizer")
+    if opt is not None:  # refuse the other optimizer family's state before anything is loaded
+        keys = {k for st in opt["state"].values() for k in st}
+        want = {"step", "exp_avg", "exp_avg_sq"} if trainer.adam else {"momentum_buffer"}
+        if keys and not keys <= want:
+            raise ValueError(f"checkpoint optimizer state {sorted(keys)} does not fit this trainer's "
+                             f"{trainer.optimizer}: 'momentum_buffer' is SGD state, 'exp_avg' / 'exp_avg_sq' / "
+                             f"'step' Adam or AdamW state; build the trainer with the optimizer the run used")
     ema = {k: (v.float() if v.is_floating_point() else v) for k, v in ckpt["ema"].items()}
     # the model resumes from the EMA weights (reference: attempt_load_weights(last) loads ckpt['ema'])
     trainer.model.load_state_dict({k: v.to(trainer.dev) for k, v in ema.items()}, strict=True)
@@ -128,9 +169,9 @@ def resume(trainer, ckpt):
         off = trainer._eoff[ei]
         trainer.ema_flat[off:off + t.numel()].copy_(ema[name].reshape(-1).to(trainer.dev))
     best_fitness = 0.0
-    opt = ckpt.get("optimizer")
     if opt is not None:
         order = _ref_param_order(trainer)
+        steps = 0
         idx = {name: i for i, (name, _p, _g, isp) in enumerate(trainer.entries) if isp}
         for k, (name, _grp) in enumerate(order):
             st = opt["state"].get(k) or opt["state"].get(str(k))
@@ -139,7 +180,14 @@ def resume(trainer, ckpt):
             ei = idx[name]
             t = trainer.entries[ei][1]
             off = trainer._goff[ei]
+            if trainer.adam:
+                trainer.mom[off:off + t.numel()].copy_(st["exp_avg"].float().reshape(-1).to(trainer.dev))
+                trainer.sq[off:off + t.numel()].copy_(st["exp_avg_sq"].float().reshape(-1).to(trainer.dev))
+                steps = max(steps, int(st["step"]))
+                continue
             trainer.mom[off:off + t.numel()].copy_(st["momentum_buffer"].float().reshape(-1).to(trainer.dev))
+        if trainer.adam:
+            trainer.opt_steps = steps
         best_fitness = ckpt.get("best_fitness") or 0.0
     trainer.updates = int(ckpt.get("updates", 0))
     trainer.packs.valid = False

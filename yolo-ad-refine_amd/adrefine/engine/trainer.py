@@ -8,6 +8,8 @@ DDP :217-273) on libadr_hip:
   [DDP] bucketed all-reduce SUM of the arena over RCCL, overlapped with the backward (engine/ddp.py)
   every `accumulate` batches (ni - last_opt_step >= accumulate, trainer.py:396):
       clip_grad_norm_(10) + SGD(momentum, nesterov=True, 3 param groups) + EMA + zero_grad   (one fused pair)
+      or, with optimizer='Adam' / 'AdamW' / 'auto' (resolve_optimizer = build_optimizer's choice), the same pair
+      with torch.optim.Adam / AdamW(betas=(momentum, 0.999)) in place of SGD (adr_opt_step_adam)
 
 `batch_size` is the reference's `self.batch_size` = args.batch, the GLOBAL batch over all ranks
 (trainer.py:290 divides it per rank); accumulate = max(round(nbs / batch_size), 1) and
@@ -22,7 +24,8 @@ LambdaLR factor lf(epoch) (linear, or one_cycle with cos_lr). Without `nb` the s
 The step can be captured once into HIP graphs (`capture(batch)`, torch.cuda.CUDAGraph over hipGraph): the
 forward + loss + backward (one graph per backward stage when the step is staged for DDP) and the optimizer tail,
 with the collectives launched between replays. Per-step scalars (lr per group, momentum, EMA decay, first-step
-flag) live in a device vector written by a stream-ordered kernel before each replay.
+flag; for Adam the bias corrections of the step being taken) live in a device vector written by a stream-ordered
+kernel before each replay. Adam's beta1 is not warmed up (its param groups have no 'momentum', trainer.py:379).
 
 Parameters that never receive a gradient (e.g. AdaptiveDynamicTanh.scale_weights, unused by the reference's
 forward) are skipped by SGD exactly like torch.optim.SGD skips p.grad is None.
@@ -61,6 +64,36 @@ DDP_BUCKET_MB = float(os.environ.get("ADR_DDP_BUCKET_MB", "8"))
 DDP_CUTS = tuple(int(v) for v in os.environ["ADR_DDP_CUTS"].split(",")) if os.environ.get("ADR_DDP_CUTS") else None
 
 
+OPTIMIZERS = ("SGD", "Adam", "AdamW")
+_UNSUPPORTED = ("Adamax", "NAdam", "RAdam", "RMSProp")  # build_optimizer accepts them; no kernel here
+
+
+def resolve_optimizer(name, lr0, momentum, warmup_bias_lr, nc, iterations):
+    """build_optimizer's name handling (trainer.py:773-805): returns (name, lr0, momentum, warmup_bias_lr).
+    'auto' ignores lr0 / momentum: more than 10000 iterations give SGD(0.01, 0.9), otherwise AdamW with
+    lr0 = round(0.002 * 5 / (4 + nc), 6) and momentum (beta1) 0.9; both set warmup_bias_lr to 0 (:782)."""
+    if name == "auto":
+        if iterations is None:
+            raise ValueError("optimizer='auto' needs `iterations` (optimizer_iterations)")
+        lr_fit = round(0.002 * 5 / (4 + nc), 6)
+        name, lr0, momentum = ("SGD", 0.01, 0.9) if iterations > 10000 else ("AdamW", lr_fit, 0.9)
+        return name, lr0, momentum, 0.0
+    if name in OPTIMIZERS:
+        return name, lr0, momentum, warmup_bias_lr
+    if name in _UNSUPPORTED:
+        raise NotImplementedError(f"Optimizer '{name}' has no fused kernel in this build; supported: "
+                                  f"[{', '.join(OPTIMIZERS)}, auto].")
+    raise NotImplementedError(
+        f"Optimizer '{name}' not found in list of available optimizers "
+        f"[Adam, AdamW, NAdam, RAdam, RMSProp, SGD, auto]."
+        "To request support for addition optimizers please visit https://github.com/ultralytics/ultralytics.")
+
+
+def optimizer_iterations(n_images, batch_size, nbs, epochs):
+    """The iteration count build_optimizer's 'auto' branch sees (trainer.py:307)."""
+    return math.ceil(n_images / max(batch_size, nbs)) * epochs
+
+
 def param_groups(model):
     """build_optimizer grouping (trainer.py:781-789): 'bias' in name -> g2; norm-layer weights -> g1; else g0."""
     g = [], [], []
@@ -84,9 +117,12 @@ class Schedule:
     (g2, g0, g1), so its `j == 0` warm-up bias rule applies to g2 here."""
 
     def __init__(self, lr0=0.01, lrf=0.01, momentum=0.937, nbs=64, batch_size=64, epochs=100, nb=None,
-                 warmup_epochs=3.0, warmup_bias_lr=0.1, warmup_momentum=0.8, cos_lr=False):
+                 warmup_epochs=3.0, warmup_bias_lr=0.1, warmup_momentum=0.8, cos_lr=False, warm_momentum=True):
         self.lr0, self.lrf, self.momentum, self.epochs, self.nb = lr0, lrf, momentum, epochs, nb
         self.cos_lr = cos_lr
+        # trainer.py:379 warms the momentum up only `if "momentum" in x`: Adam's param groups carry `betas`, so
+        # beta1 stays at `momentum` from batch 0 (warm_momentum=False)
+        self.warm_momentum = warm_momentum
         self.warmup_bias_lr, self.warmup_momentum = warmup_bias_lr, warmup_momentum
         self.acc_target = nbs / batch_size
         self.accumulate0 = max(round(nbs / batch_size), 1)  # trainer.py:305
@@ -108,7 +144,8 @@ class Schedule:
             acc = max(1, int(np.interp(ni, xi, [1, self.acc_target]).round()))
             lr_bias = float(np.interp(ni, xi, [self.warmup_bias_lr, target]))
             lr_w = float(np.interp(ni, xi, [0.0, target]))
-            mom = float(np.interp(ni, xi, [self.warmup_momentum, self.momentum]))
+            mom = float(np.interp(ni, xi, [self.warmup_momentum, self.momentum])) if self.warm_momentum \
+                else self.momentum
             return [lr_w, lr_w, lr_bias], mom, acc
         if self.nw >= 0:  # after warm-up accumulate keeps its last interpolated value
             acc = max(1, int(np.interp(self.nw, [0, self.nw], [1, self.acc_target]).round()))
@@ -126,7 +163,20 @@ class FusedTrainer:
     def __init__(self, model, lr0=0.01, momentum=0.937, weight_decay=5e-4, nbs=64, batch_size=64, world_size=1,
                  process_group=None, ema=True, ema_decay=0.9999, ema_tau=2000, max_norm=10.0, epochs=100, nb=None,
                  lrf=0.01, warmup_epochs=3.0, warmup_bias_lr=0.1, warmup_momentum=0.8, cos_lr=False, stages=None,
-                 collectives=None):
+                 collectives=None, optimizer="SGD", nc=None, iterations=None):
+        """optimizer: 'SGD' (default), 'Adam', 'AdamW' or 'auto' (resolve_optimizer; needs `iterations`, see
+        optimizer_iterations). For Adam / AdamW `momentum` is beta1, as build_optimizer's betas=(momentum, 0.999).
+        nc (used by 'auto' only) defaults to the detection head's nc: the reference's getattr(model, "nc", 10)
+        reads the attribute its detection trainer attaches before build_optimizer runs (models/yolo/detect/train.py:81,
+        model.nc = data["nc"]), and the head is built with that same class count — so the head's nc is what the
+        reference sees for a model that has one; the fallback 10 applies only to a model without a detection head."""
+        if nc is None:
+            nc = getattr(model, "nc", None) or getattr(getattr(model, "model", [None])[-1], "nc", 10)
+        optimizer, lr0, momentum, warmup_bias_lr = resolve_optimizer(optimizer, lr0, momentum, warmup_bias_lr, nc,
+                                                                     iterations)
+        self.optimizer = optimizer
+        self.adam = optimizer != "SGD"
+        self.beta2, self.eps = 0.999, 1e-8  # build_optimizer: betas=(momentum, 0.999), torch's default eps
         self.model = model
         self.world_size = world_size
         # collectives=True issues the bucket all-reduces even at world_size 1 (a one-rank RCCL group exercises the
@@ -136,7 +186,7 @@ class FusedTrainer:
         self.max_norm = max_norm
         self.batch_size = batch_size
         self.sched = Schedule(lr0, lrf, momentum, nbs, batch_size, epochs, nb, warmup_epochs, warmup_bias_lr,
-                              warmup_momentum, cos_lr)
+                              warmup_momentum, cos_lr, warm_momentum=not self.adam)
         self.accumulate = self.sched.accumulate0
         self.wd = weight_decay * batch_size * self.accumulate / nbs  # trainer.py:305-306
         self.lr, self.momentum, _ = self.sched.at(0)
@@ -155,7 +205,11 @@ class FusedTrainer:
         self.entries = [(name, p, gi, True) for name, p, gi in plist]
         self.nparam = sum(p.numel() for _, p, _, _ in self.entries)
         self.grad = torch.zeros(self.nparam, dtype=torch.float32, device=dev)
-        self.mom = torch.zeros(self.nparam, dtype=torch.float32, device=dev)
+        if self.adam:  # both moments in one allocation: the kernel finds exp_avg_sq at buf + nparam
+            self.opt_state = torch.zeros(2 * self.nparam, dtype=torch.float32, device=dev)
+            self.mom, self.sq = self.opt_state[:self.nparam], self.opt_state[self.nparam:]
+        else:
+            self.mom = torch.zeros(self.nparam, dtype=torch.float32, device=dev)
         off = 0
         self._goff = []
         bounds = [[None, None] for _ in range(nst)]
@@ -197,6 +251,7 @@ class FusedTrainer:
         self.norm = torch.zeros(1, dtype=torch.float32, device=dev)
         self.tab_dev = None
         self.updates = 0
+        self.opt_steps = 0  # optimizer steps taken: torch's per-parameter `step` (the EMA's count is `updates`)
         self.ema_decay = ema_decay
         self.ema_tau = ema_tau
         self.hyper = torch.zeros(16, dtype=torch.float32, device=dev)
@@ -239,14 +294,32 @@ class FusedTrainer:
             staged_backward(loss, bounds, run, after_stage or (lambda s: None))
         return items
 
+    def adam_scalars(self):
+        """(step_size per group, bc2_sqrt) of the step about to be taken, in Python floats exactly as
+        torch.optim.adam._single_tensor_adam computes them for step t = opt_steps + 1."""
+        t = self.opt_steps + 1
+        bc1 = 1 - self.momentum ** t
+        bc2 = 1 - self.beta2 ** t
+        return [lr / bc1 for lr in self.lr], bc2 ** 0.5
+
     def _set_hyper(self):
         d = self.ema_decay * (1 - math.exp(-(self.updates + 1) / self.ema_tau))
-        vals = [self.lr[0], self.lr[1], self.lr[2], self.wd, 0.0, 0.0, self.momentum, 1.0,
-                1.0 if self.updates == 0 else 0.0, d]
+        if self.adam:
+            ss, bc2_sqrt = self.adam_scalars()
+            vals = [self.lr[0], self.lr[1], self.lr[2], self.wd, 0.0, 0.0, 1 - self.momentum, self.beta2,
+                    1 - self.beta2, self.eps, ss[0], ss[1], ss[2], bc2_sqrt, d,
+                    1.0 if self.optimizer == "AdamW" else 0.0]
+        else:
+            vals = [self.lr[0], self.lr[1], self.lr[2], self.wd, 0.0, 0.0, self.momentum, 1.0,
+                    1.0 if self.updates == 0 else 0.0, d]
         arr = (ctypes.c_float * len(vals))(*vals)
         lib.adr_set_f32(K.fptr(self.hyper), ctypes.cast(arr, ctypes.c_void_p), len(vals), K.stream())
 
     def _opt(self):
+        if self.adam:
+            lib.adr_opt_step_adam(K.fptr(self.tab_dev), K.fptr(self.chunks_dev), self.nchunks, K.fptr(self.partial),
+                                  float(self.max_norm), K.fptr(self.hyper), self.nparam, K.fptr(self.norm), K.stream())
+            return
         lib.adr_opt_step(K.fptr(self.tab_dev), K.fptr(self.chunks_dev), self.nchunks, K.fptr(self.partial),
                          float(self.max_norm), K.fptr(self.hyper), K.fptr(self.norm), K.stream())
 
@@ -303,6 +376,7 @@ class FusedTrainer:
         if opt_now:
             self.packs.valid = False  # weights changed: the next forward repacks
             self.updates += 1
+            self.opt_steps += 1
             self.last_opt_step = self.ni
         self.ni += 1
         return items.detach()

@@ -1,6 +1,7 @@
 // Fused trainer tail (reference engine/trainer.py:580-588 optimizer_step, :753-813 build_optimizer,
 // utils/torch_utils.py:521-546 ModelEMA): multi-tensor gradient-norm clip (clip_grad_norm_ max_norm 10),
-// SGD with Nesterov momentum and per-group weight decay / lr (torch.optim.SGD semantics), and the EMA of every
+// SGD with Nesterov momentum and per-group weight decay / lr (torch.optim.SGD semantics) or Adam / AdamW
+// (torch.optim.Adam / AdamW semantics, adr_opt_step_adam), and the EMA of every
 // floating-point model state entry, in two launches over a chunk table. Deterministic: the global norm is a
 // fixed-order reduction of per-chunk partials, recomputed identically by every block.
 #include "adr_common.h"
@@ -113,6 +114,88 @@ __global__ void __launch_bounds__(256) sgd_ema_kernel(const OptEntry* tab, const
   }
 }
 
+// Adam / AdamW tail (torch.optim.adam._single_tensor_adam, non-capturable path, amsgrad off) over the same tables.
+// hyper (device): [lr0, lr1, lr2, wd0, wd1, wd2, 1-beta1, beta2, 1-beta2, eps, ss0, ss1, ss2, bc2_sqrt, ema_d,
+// decoupled] with ss_g = lr_g / (1 - beta1^t) and bc2_sqrt = sqrt(1 - beta2^t), computed by the host for step t as
+// torch does and read from memory, so a captured graph sees each step's bias corrections. beta1 travels as its
+// complement, the only form torch's lerp_ uses, and 1 - beta2 comes from the host too: both are rounded from the
+// double difference as torch rounds them (1.f - 0.999f is off by 5e-5 relative). First moment in e.buf, second moment
+// at e.buf + sq_offset. Every operation rounds once, in torch's order: no FMA contraction, IEEE sqrt and divide.
+__global__ void __launch_bounds__(256) adam_ema_kernel(const OptEntry* tab, const OptChunk* chunks, int nchunks,
+                                                       const float* partial, float max_norm,
+                                                       const float* __restrict__ hyper, long sq_offset,
+                                                       float* norm_out) {
+#pragma clang fp contract(off)
+  const float w1 = hyper[6], beta2 = hyper[7], w2 = hyper[8], eps = hyper[9], bc2_sqrt = hyper[13];
+  const float ema_d = hyper[14];
+  const int decoupled = hyper[15] != 0.f;
+  __shared__ double sh[256];
+  __shared__ float coef_s;
+  double s = 0.0;
+  for (int k = threadIdx.x; k < nchunks; k += 256) s += partial[k];
+  sh[threadIdx.x] = s;
+  __syncthreads();
+  for (int o = 128; o > 0; o >>= 1) {
+    if (threadIdx.x < o) sh[threadIdx.x] += sh[threadIdx.x + o];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) {
+    // SGD's coefficient min(1, max_norm / (norm + 1e-6)), evaluated in double from the double sum and rounded
+    // once: gv * gv doubles the coefficient's relative error in the second moment, which sqrt(v) never forgets
+    const double tn = sqrt(sh[0]);
+    const double c = max_norm > 0.f ? (double)max_norm / (tn + 1e-6) : 1.0;
+    coef_s = (float)(c < 1.0 ? c : 1.0);
+    if (blockIdx.x == 0 && norm_out) norm_out[0] = (float)tn;
+  }
+  __syncthreads();
+  const float coef = coef_s;
+  const OptChunk ck = chunks[blockIdx.x];
+  const OptEntry e = tab[ck.entry];
+  const int gi = e.group == 0 ? 0 : (e.group == 1 ? 1 : 2);
+  const float lr = hyper[gi], wd = hyper[3 + gi], step_size = hyper[10 + gi];
+  const float shrink = 1.f - lr * wd;
+  // the SGD kernel's shape with one more stream: 5*U loads in flight per lane before the round's first store
+  constexpr int U = 4;
+  const bool upd = e.g && e.group < 3;
+  float* const sq = e.buf + sq_offset;
+  const long end = ck.start + ck.len;
+  for (long i0 = ck.start + threadIdx.x; i0 < end; i0 += 256 * U) {
+    float p[U], g[U], m1[U], m2[U], m[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const long i = i0 + 256 * u;
+      const bool in = i < end;
+      p[u] = in ? e.p[i] : 0.f;
+      g[u] = in && upd ? e.g[i] : 0.f;
+      m1[u] = in && upd ? e.buf[i] : 0.f;
+      m2[u] = in && upd ? sq[i] : 0.f;
+      m[u] = in && e.ema ? e.ema[i] : 0.f;
+    }
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const long i = i0 + 256 * u;
+      if (i >= end) break;
+      float pv = p[u];
+      if (upd) {
+        float gv = g[u] * coef;
+        if (wd != 0.f) {
+          if (decoupled) pv *= shrink;  // AdamW: param.mul_(1 - lr * weight_decay)
+          else gv += wd * pv;           // Adam: grad.add(param, alpha=weight_decay)
+        }
+        const float mv = m1[u] + (gv - m1[u]) * w1;      // exp_avg.lerp_(grad, 1 - beta1)
+        const float vv = m2[u] * beta2 + w2 * gv * gv;   // exp_avg_sq.mul_(beta2).addcmul_(grad, grad, value=1 - beta2)
+        const float denom = sqrtf(vv) / bc2_sqrt + eps;
+        pv -= step_size * (mv / denom);
+        e.buf[i] = mv;
+        sq[i] = vv;
+        e.g[i] = 0.f;  // optimizer.zero_grad()
+        e.p[i] = pv;
+      }
+      if (e.ema) e.ema[i] = ema_d * m[u] + (1.f - ema_d) * pv;
+    }
+  }
+}
+
 // gather scattered tensors into a flat buffer (DDP bucket) or scatter back
 __global__ void __launch_bounds__(256) flat_copy_kernel(const OptEntry* tab, const OptChunk* chunks, float* flat,
                                                         const long* offsets, int to_flat) {
@@ -141,6 +224,18 @@ extern "C" int adr_opt_step(const void* tab, const void* chunks, int nchunks, fl
   hipLaunchKernelGGL(sgd_ema_kernel, dim3(nchunks), dim3(256), 0, st, (const OptEntry*)tab, (const OptChunk*)chunks,
                      nchunks, partial, max_norm, hyper, norm_out);
   return check_launch("adr_opt_step");
+}
+
+extern "C" int adr_opt_step_adam(const void* tab, const void* chunks, int nchunks, float* partial, float max_norm,
+                                 const float* hyper, long sq_offset, float* norm_out, void* stream) {
+  ADR_REQUIRE(nchunks > 0, "opt_step_adam: empty chunk table");
+  ADR_REQUIRE(tab && chunks && partial && hyper, "opt_step_adam: null table, partials or hyper");
+  hipStream_t st = (hipStream_t)stream;
+  hipLaunchKernelGGL(grad_sqnorm_kernel, dim3(nchunks), dim3(256), 0, st, (const OptEntry*)tab,
+                     (const OptChunk*)chunks, partial);
+  hipLaunchKernelGGL(adam_ema_kernel, dim3(nchunks), dim3(256), 0, st, (const OptEntry*)tab, (const OptChunk*)chunks,
+                     nchunks, partial, max_norm, hyper, sq_offset, norm_out);
+  return check_launch("adr_opt_step_adam");
 }
 
 struct F32x16 {
