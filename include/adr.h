@@ -551,6 +551,17 @@ int adr_dcn_bwd_bf16_levels(const adr_dcn_level* lv, int levels, int xcs, int om
 int adr_augment_u8(const void* pool, const void* descs, int B, const int* tables, const void* luts, void* out, int H,
                    int W, void* stream);
 int adr_augment_desc_size(void);
+/* The same chain with MixUp (data/augment.py:866-949) between the warp and RandomHSV. descs: ndesc >= B device
+ * adr_aug_desc records, the B images' own first, then the second layers' (of which only tiles, canvas, warp and
+ * tab_off are read); mix: B device records {int second; int pad; double r; double one_minus_r} (size
+ * adr_augment_mix_desc_size()) and mix_host the same records in host memory (validated here: second is -1, the image
+ * is not mixed, or in [B, ndesc)). A mixed pixel is (uint8)((double)a * r + (double)b * one_minus_r): two float64
+ * products and one sum, each rounded, truncated toward zero, as numpy evaluates img1 * r + img2 * (1 - r); the flips,
+ * the LUTs and the channel order of the image's own descriptor then act on the blend. adr_augment_u8 is untouched:
+ * a batch without a mixed image takes it. */
+int adr_augment_mix_u8(const void* pool, const void* descs, int ndesc, const void* mix, const void* mix_host, int B,
+                       const int* tables, const void* luts, void* out, int H, int W, void* stream);
+int adr_augment_mix_desc_size(void);
 /* LetterBox pixels (data/augment.py:1475-1640; the validation transform data/dataset.py:181, RandomPerspective's
  * pre_transform after close_mosaic, the predictor's pre_transform + preprocess engine/predictor.py:125, 144-156):
  * cv2.resize(INTER_LINEAR) to the unpadded size -> cv2.copyMakeBorder(constant 114) -> optional BGR -> RGB ->

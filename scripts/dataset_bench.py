@@ -3,7 +3,11 @@ resident sources against the same plans rendered from host numpy sources (the pa
 throughput beside a training step. No number is promised; the one requirement is (c): the resident path is not slower
 than the host-source path of the same run on the same device.
 
-  python scripts/dataset_bench.py [--out profiles/dataset_bench.json] [--n 512]     (run it under `timeout`)
+  python scripts/dataset_bench.py [--out profiles/dataset_bench.json] [--n 512] [--mixup P]   (run it under `timeout`)
+
+--mixup P (default 0: the rows as they have always been measured) sets hyp.mixup: a sample is then mixed with
+probability P (two layers, adr_augment_mix_u8). With P > 0 the result does not replace the file: it is stored in it
+under the key "mixup_P", next to the existing rows.
 
 Input: a synthetic directory of --n PNGs around 1280 x 720 (five sizes) with 1-8 labels each, written to a temporary
 directory; imgsz 640, batch 64, the default hyp. Medians of 20 batches after 3 warm-ups, HIP events and host wall
@@ -76,6 +80,7 @@ def main():
     ap.add_argument("--out", default=str(ROOT / "profiles" / "dataset_bench.json"))
     ap.add_argument("--n", type=int, default=512)
     ap.add_argument("--no-train", action="store_true", help="skip (d)")
+    ap.add_argument("--mixup", type=float, default=0.0, help="hyp.mixup; > 0: stored under the key mixup_P")
     args = ap.parse_args()
     assert torch.cuda.is_available(), "dataset_bench needs the GPU"
     from recipe import AUG_HYPS
@@ -85,8 +90,11 @@ def main():
     from adrefine.data.dataset import YOLODataset, load_bgr
     from adrefine.data.pool import DevicePool
 
-    hyp = lambda: SimpleNamespace(**AUG_HYPS["default"], mask_ratio=4, overlap_mask=True)  # noqa: E731
+    hyp = lambda: SimpleNamespace(**dict(AUG_HYPS["default"], mixup=args.mixup), mask_ratio=4,  # noqa: E731
+                                  overlap_mask=True)
     res = {"imgsz": IMGSZ, "batch": BS, "images": args.n, "device": torch.cuda.get_device_name(0)}
+    if args.mixup > 0:
+        res["mixup"] = args.mixup
     with tempfile.TemporaryDirectory() as tmp:
         t0 = time.perf_counter()
         tree = write_dataset(Path(tmp) / "syn", args.n)
@@ -172,6 +180,8 @@ def main():
             for p in ps:
                 q = copy.copy(p)
                 q.tiles = [(host[id(t[0])],) + tuple(t[1:]) for t in p.tiles]
+                if p.mix is not None:
+                    q.mix = (on_host([p.mix[0]])[0],) + p.mix[1:]
                 out.append(q)
             return out
 
@@ -180,6 +190,8 @@ def main():
         r_dev = timed([lambda ps=ps: render(ps) for ps in plans])
         r_host = timed([lambda ps=ps: render(ps, "cuda") for ps in hplans])
         r_dev2 = timed([lambda ps=ps: render(ps) for ps in plans])
+        if args.mixup > 0:
+            res["mixed_samples_per_batch"] = statistics.mean(sum(p.mix is not None for p in ps) for ps in plans)
         res["render_batch"] = {"resident": r_dev, "host_sources": r_host, "resident_again": r_dev2, "identical": same,
                                "resident_not_slower": min(r_dev["wall_median_ms"], r_dev2["wall_median_ms"]) <=
                                r_host["wall_median_ms"]}
@@ -208,6 +220,8 @@ def main():
                 dt = time.perf_counter() - t0
                 res[f"loader_with_step_prefetch{prefetch}"] = {"images_per_s": nimg / dt, "ms_per_batch": dt / (nimg / BS) * 1e3}
     Path(args.out).parent.mkdir(parents=True, exist_ok=True)
+    if args.mixup > 0 and Path(args.out).exists():  # beside the mixup 0 rows, which stay as they were measured
+        res = dict(json.loads(Path(args.out).read_text()), **{f"mixup_{args.mixup:g}": res})
     Path(args.out).write_text(json.dumps(res, indent=1) + "\n")
     print(json.dumps(res))
 

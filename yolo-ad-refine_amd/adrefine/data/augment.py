@@ -4,14 +4,17 @@ the GPU.
 The transforms keep the reference's classes, constructor arguments, RNG calls (python `random` / `np.random`, same
 order, same count) and label arithmetic (numpy, bit-identical boxes through adrefine.data.instance). What they do
 NOT do is touch pixels: `labels["img"]` is an ImagePlan — the recipe of the image (mosaic tiles over source images,
-the warpAffine matrix, the HSV LUTs, the flips, the channel order) — and `collate_fn` renders the whole batch with
-one launch of adr_augment_u8 (csrc/adr_augment.hip) straight into the uint8 (B, 3, H, W) tensor the trainer reads
+the warpAffine matrix, MixUp's second layer and ratio, the HSV LUTs, the flips, the channel order) — and `collate_fn`
+renders the whole batch with one launch of adr_augment_u8, or of adr_augment_mix_u8 when a sample of it is mixed
+(csrc/adr_augment.hip), straight into the uint8 (B, 3, H, W) tensor the trainer reads
 (FusedTrainer takes uint8 batches, /255 in the stem). The 2s x 2s mosaic canvas, the warped and the HSV images of
 the reference never exist.
 
 Covered (detection, the default hyp of cfg/default.yaml and any degrees / translate / scale / shear / flip / HSV
-gains): Mosaic (n=4, p=1), CopyPaste (p=0 or no segments), RandomPerspective (perspective 0: warpAffine), MixUp
-(p=0), Albumentations (absent package: no-op, as in the reference without albumentations installed), RandomHSV,
+gains): Mosaic (n=4), CopyPaste (p=0 or no segments), RandomPerspective (perspective 0: warpAffine), MixUp (any p:
+the second sample through the same pre_transform, np.random.beta(32, 32), labels concatenated, the float64 blend
+(img1 * r + img2 * (1 - r)).astype(np.uint8) evaluated per pixel by the kernel, two products and a sum without FMA,
+truncated), Albumentations (absent package: no-op, as in the reference without albumentations installed), RandomHSV,
 RandomFlip, Format; LetterBox (every constructor argument; rect_shape, ratio_pad and the label update), as
 RandomPerspective's pre_transform when mosaic is off (mosaic p < 1, close_mosaic), as the validation transform
 (build_transforms with augment off) and on raw images of any size (render_letterbox, FusedPredictor.predict_images).
@@ -19,9 +22,8 @@ A LetterBox that only pads (the shape already equals new_unpad: every dataset-fe
 BaseDataset.load_image leaves the long side at imgsz) is a canvas with one tile and goes through adr_augment_u8 with
 the rest of the chain; a LetterBox that resizes is rendered by adr_letterbox_u8 (csrc/adr_letterbox.hip: cv2.resize
 INTER_LINEAR in OpenCV's fixed point + constant border + RGB / CHW). Not covered (raise): a LetterBox resize followed
-by warp / HSV / flip in one plan (cannot arise from a dataset), warpPerspective, MixUp or CopyPaste with p > 0,
-mosaic9, segments / keypoints. Source images come in resized as BaseDataset.load_image leaves them
-(data/base.py:151-190): host arrays (uploaded with the batch), or DeviceImages of one data/pool.py DevicePool,
+by warp / HSV / flip in one plan (cannot arise from a dataset), warpPerspective, CopyPaste with p > 0, mosaic9,
+segments / keypoints. Source images come in resized as BaseDataset.load_image leaves them (data/base.py:151-190): host arrays (uploaded with the batch), or DeviceImages of one data/pool.py DevicePool,
 decoded on the host once, resized by adr_resize_u8 and resident in HBM (data/dataset.py YOLODataset): then a batch
 uploads descriptors and tables only."""
 from __future__ import annotations
@@ -43,8 +45,9 @@ __all__ = ["ImagePlan", "Compose", "Mosaic", "CopyPaste", "RandomPerspective", "
 
 class ImagePlan:
     """A deferred uint8 BGR HWC image (see the module docstring). Stages must come in the chain's order:
-    canvas (source / mosaic / letterbox) -> warp -> hsv -> flips -> channel order. A letterbox that resizes is a
-    stage of its own (`resize`), followed by the channel order only."""
+    canvas (source / mosaic / letterbox) -> warp -> mix -> hsv -> flips -> channel order. A letterbox that resizes is
+    a stage of its own (`resize`), followed by the channel order only. The mix stage (MixUp) holds a second layer: a
+    plan of the same size with a canvas and at most a warp."""
 
     def __init__(self, src: np.ndarray):
         if src.dtype != np.uint8 or src.ndim != 3 or src.shape[2] != 3:
@@ -56,6 +59,7 @@ class ImagePlan:
         self.resize = None  # (nw, nh, left, top): LetterBox's cv2.resize of the canvas to (nw, nh), placed at (left, top)
         self.ratio_pad = None  # LetterBox: ((ratio_w, ratio_h), (left, top))
         self.M = None  # 2x3 float32 warpAffine matrix (canvas -> output)
+        self.mix = None  # MixUp: (second layer ImagePlan, r, 1 - r), both ratios float64 from the host
         self.lut = None  # (3, 256) uint8
         self.flip_ud = self.flip_lr = False
         self.rgb = False
@@ -68,8 +72,27 @@ class ImagePlan:
         if self.resize is not None:
             raise NotImplementedError(f"ImagePlan: {what} after a LetterBox that resizes (cv2.resize is not fused into "
                                       "the later stages; images from a dataset are already at new_unpad: pad only)")
-        if not ok:
+        if not ok or (self.mix is not None and what not in ("hsv", "flip")):
             raise NotImplementedError(f"ImagePlan: {what} out of the supported chain order")
+
+    def _layer_only(self):
+        """Canvas and at most a warp: what a layer of a mix may be."""
+        return self.lut is None and not (self.flip_ud or self.flip_lr) and self.resize is None and self.mix is None
+
+    def layers(self):
+        """The plans whose tiles the image reads: itself, and the second layer of a mix."""
+        return (self,) if self.mix is None else (self, self.mix[0])
+
+    def mixup(self, second, r):
+        """(img1 * r + img2 * (1 - r)).astype(np.uint8) (MixUp._mix_transform, augment.py:943-945) with this plan as
+        img1: uint8 arrays times a float64, so two float64 products and a float64 sum, truncated. 1 - r is taken here,
+        in float64, once."""
+        self._stage(self._layer_only(), "mix")
+        second._stage(second._layer_only(), "mix")
+        if second.size != self.size:
+            raise NotImplementedError(f"ImagePlan: mix of images of sizes {self.size} and {second.size}")
+        r = float(r)
+        self.mix = (second, r, 1 - r)
 
     def letterbox(self, new_unpad, left, top, right, bottom):
         """The plan of cv2.copyMakeBorder(cv2.resize(image, new_unpad) if its size differs, top, bottom, left, right,
@@ -106,8 +129,9 @@ def _plan(img):
 
 
 def _source_pool(plans, what):
-    """The DevicePool every tile source of the batch lives in, or None when all of them are host arrays."""
-    srcs = [t[0] for p in plans for t in p.tiles]
+    """The DevicePool every tile source of the batch (of both layers of a mixed image) lives in, or None when all of
+    them are host arrays."""
+    srcs = [t[0] for p in plans for q in p.layers() for t in q.tiles]
     dev = [s for s in srcs if _is_device(s)]
     if not dev:
         return None
@@ -198,7 +222,8 @@ class Mosaic(BaseMixTransform):
         for i in range(4):
             patch = labels if i == 0 else labels["mix_labels"][i - 1]
             src = _plan(patch["img"])
-            if len(src.tiles) != 1 or src.M is not None or src.lut is not None or src.resize is not None:
+            if len(src.tiles) != 1 or src.M is not None or src.lut is not None or src.resize is not None \
+                    or src.mix is not None:
                 raise NotImplementedError("Mosaic tiles must be untransformed source images")
             img = src.tiles[0][0]
             h, w = patch.pop("resized_shape")
@@ -263,7 +288,8 @@ class CopyPaste(BaseMixTransform):
 
 
 class MixUp(BaseMixTransform):
-    """augment.py:866-949: the draw of BaseMixTransform.__call__ happens; p > 0 is not covered."""
+    """augment.py:866-949: the second sample goes through pre_transform (its own mosaic / letterbox and warp draws),
+    np.random.beta gives the ratio, the labels are concatenated; the blend becomes the plan's mix stage."""
 
     def __init__(self, dataset, pre_transform=None, p=0.0):
         super().__init__(dataset=dataset, pre_transform=pre_transform, p=p)
@@ -272,7 +298,14 @@ class MixUp(BaseMixTransform):
         return random.randint(0, len(self.dataset) - 1)
 
     def _mix_transform(self, labels):
-        raise NotImplementedError("MixUp with p > 0")
+        r = np.random.beta(32.0, 32.0)  # mixup ratio, alpha=beta=32.0
+        labels2 = labels["mix_labels"][0]
+        img = _plan(labels["img"])
+        img.mixup(_plan(labels2["img"]), r)
+        labels["img"] = img
+        labels["instances"] = Instances.concatenate([labels["instances"], labels2["instances"]], axis=0)
+        labels["cls"] = np.concatenate([labels["cls"], labels2["cls"]], 0)
+        return labels
 
 
 class Albumentations:
@@ -605,8 +638,15 @@ class AugDesc(ctypes.Structure):
         "ntile", "cw", "ch", "warp", "tab_off", "lut_off", "flip_ud", "flip_lr", "rgb", "pad_")]
 
 
+class AugMix(ctypes.Structure):
+    """adr_augment_mix_u8's per-image record (include/adr.h)."""
+    _fields_ = [("second", ctypes.c_int), ("pad_", ctypes.c_int), ("r", ctypes.c_double),
+                ("one_minus_r", ctypes.c_double)]
+
+
 def render(plans, device="cuda", out=None):
-    """Run adr_augment_u8 for a list of ImagePlans of one output size: returns the uint8 (B, 3, H, W) batch."""
+    """Run adr_augment_u8 for a list of ImagePlans of one output size, or adr_augment_mix_u8 when one of them has a
+    mix stage: returns the uint8 (B, 3, H, W) batch."""
     from ..native import lib
     from ..kernels import stream
 
@@ -618,6 +658,13 @@ def render(plans, device="cuda", out=None):
         raise ValueError("render: every image of a batch must have the same size")
     if any(p.resize is not None for p in plans):
         raise ValueError("render: a LetterBox resize is rendered by render_letterbox (adr_letterbox_u8)")
+    mixed = [b for b, p in enumerate(plans) if p.mix is not None]
+    if mixed and ctypes.sizeof(AugMix) != lib.adr_augment_mix_desc_size():
+        raise RuntimeError("adr_augment_mix_u8's mix record layout mismatch between adrefine and libadr_hip")
+    for b in mixed:
+        q = plans[b].mix[0]
+        if q.size != (W, H) or not q._layer_only():
+            raise ValueError(f"render: image {b}'s second layer is not a canvas / warp plan of the batch's size")
     resident = _source_pool(plans, "render")  # sources already in HBM: no pixels are uploaded
     if resident is not None:
         if out is not None and not _same_device(out.device, resident.device):
@@ -625,11 +672,13 @@ def render(plans, device="cuda", out=None):
         resident.flush()
         device = resident.device
     srcs, index = [], {}
-    descs = (AugDesc * B)()
+    descs = (AugDesc * (B + len(mixed)))()  # the images' own descriptors, then the second layers'
+    mix = (AugMix * B)()
     tabs, luts = [], []
     off = ntab = 0
-    for b, p in enumerate(plans):
-        d = descs[b]
+
+    def layer(d, p):  # canvas and warp of one layer; a source shared by layers or images is uploaded once
+        nonlocal off, ntab
         if len(p.tiles) > 4:
             raise ValueError("render: at most four tiles per image")
         d.ntile = len(p.tiles)
@@ -654,10 +703,20 @@ def render(plans, device="cuda", out=None):
             d.tab_off = ntab
             tabs.append(tab.astype(np.int32))
             ntab += tab.size
+        d.lut_off = -1
+
+    for b, p in enumerate(plans):
+        d = descs[b]
+        layer(d, p)
         d.lut_off = -1 if p.lut is None else 768 * len(luts)
         if p.lut is not None:
             luts.append(p.lut.reshape(-1))
         d.flip_ud, d.flip_lr, d.rgb = int(p.flip_ud), int(p.flip_lr), int(p.rgb)
+        mix[b].second = -1
+    for k, b in enumerate(mixed):
+        q, r, one_minus_r = plans[b].mix
+        layer(descs[B + k], q)
+        mix[b].second, mix[b].r, mix[b].one_minus_r = B + k, r, one_minus_r
     if resident is not None:
         pool = resident.tensor
     else:
@@ -667,10 +726,18 @@ def render(plans, device="cuda", out=None):
     lt = torch.from_numpy(np.concatenate(luts) if luts else np.zeros(1, np.uint8)).to(device, non_blocking=True)
     if out is None:
         out = torch.empty(B, 3, H, W, dtype=torch.uint8, device=device)
-    lib.adr_augment_u8(ctypes.c_void_p(pool.data_ptr()), ctypes.c_void_p(dd.data_ptr()), B,
-                       ctypes.c_void_p(tb.data_ptr()), ctypes.c_void_p(lt.data_ptr()), ctypes.c_void_p(out.data_ptr()),
-                       H, W, stream())
-    out._adr_keep = (pool, dd, tb, lt)  # the inputs live until the launch has read them (stream order)
+    if not mixed:  # the launch a batch without MixUp has always taken
+        lib.adr_augment_u8(ctypes.c_void_p(pool.data_ptr()), ctypes.c_void_p(dd.data_ptr()), B,
+                           ctypes.c_void_p(tb.data_ptr()), ctypes.c_void_p(lt.data_ptr()),
+                           ctypes.c_void_p(out.data_ptr()), H, W, stream())
+        out._adr_keep = (pool, dd, tb, lt)  # the inputs live until the launch has read them (stream order)
+        return out
+    mm = torch.frombuffer(bytearray(mix), dtype=torch.uint8).to(device, non_blocking=True)
+    lib.adr_augment_mix_u8(ctypes.c_void_p(pool.data_ptr()), ctypes.c_void_p(dd.data_ptr()), len(descs),
+                           ctypes.c_void_p(mm.data_ptr()), ctypes.cast(mix, ctypes.c_void_p), B,
+                           ctypes.c_void_p(tb.data_ptr()), ctypes.c_void_p(lt.data_ptr()),
+                           ctypes.c_void_p(out.data_ptr()), H, W, stream())
+    out._adr_keep = (pool, dd, mm, tb, lt)
     return out
 
 
@@ -685,8 +752,9 @@ LB_COPY, LB_LINEAR, LB_AREA2 = 0, 1, 2
 
 def _letterbox_geometry(p):
     """(src, nw, nh, left, top) of a plan adr_letterbox_u8 can render; src None: nothing but the 114 fill."""
-    if p.M is not None or p.lut is not None or p.flip_ud or p.flip_lr or len(p.tiles) > 1:
-        raise ValueError("render_letterbox: the plan has mosaic / warp / HSV / flip stages (render() takes those)")
+    if p.M is not None or p.lut is not None or p.flip_ud or p.flip_lr or len(p.tiles) > 1 or p.mix is not None:
+        raise ValueError("render_letterbox: the plan has mosaic / warp / mix / HSV / flip stages (render() takes "
+                         "those)")
     if not p.tiles:
         return None, 0, 0, 0, 0
     src, x1a, y1a, x2a, y2a, x1b, y1b = p.tiles[0]

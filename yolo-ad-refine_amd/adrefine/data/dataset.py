@@ -174,6 +174,7 @@ class YOLODataset:
         if self.cache not in (None, "gpu"):
             raise ValueError(f"YOLODataset: cache={cache!r}")
         self.inflight = max(1, int(inflight))
+        self._hyp = hyp  # pool_slots reads mixup
         self._retired, self._seq, self._rlock = [], 0, threading.Lock()
         self.batches_built = 0  # the loaders' batch counter (begin_batch / end_batch)
         self.pool = pool
@@ -313,11 +314,15 @@ class YOLODataset:
     # ---- images ----
     def pool_slots(self):
         """Images a cache=None pool must hold. Training: the buffer + the batches in flight, whose evicted images wait
-        for their render (at most one eviction per sample). Validation: one batch more, since an image stays until the
-        batch after its own has been rendered. `inflight` batches at most are begun and not yet ended: the loader
-        admits a new batch only then (build.py DataLoader._admit)."""
+        for their render. Only a load_image call that finds its image absent evicts, one image at most, and a sample
+        makes one such call (its own index; the mosaic's other three come out of the buffer, resident by
+        construction), or two with MixUp (hyp.mixup > 0: the second sample's random.randint index as well, whose
+        mosaic again draws from the buffer): at most one, or two, evictions per sample. Validation: one batch more,
+        since an image stays until the batch after its own has been rendered. `inflight` batches at most are begun
+        and not yet ended: the loader admits a new batch only then (build.py DataLoader._admit)."""
         batches = self.inflight + (0 if self.augment else 1)
-        return self.max_buffer_length + batches * self.batch_size
+        loads = 2 if self.augment and not self.rect and getattr(self._hyp, "mixup", 0.0) > 0 else 1
+        return self.max_buffer_length + batches * self.batch_size * loads
 
     def source_hw(self, i):
         """(h0, w0) of what load_bgr will return for image i: the sibling .npy's when there is one (the reference
@@ -388,7 +393,11 @@ class YOLODataset:
     # An image that leaves (evicted from the buffer, or a validation image) may still be a tile of a sample that has
     # not been rendered, so its block goes back to the pool only once that batch has: begin_batch(k) names the batch
     # under construction, end_batch(k) (after batch k's render was enqueued) frees what was retired up to it. Stream
-    # order then makes the reuse safe: the next resize into the block runs behind the render that read it.
+    # order then makes the reuse safe: the next resize into the block runs behind the render that read it. This does not
+# depend on how many source images a sample has (four for a mosaic, up to eight for a MixUp of two mosaics, any of
+# which a later load of the same sample may evict): a sample of batch k holds only images that were resident while it
+# was built, so each of them is retired, if at all, under a batch number >= k, and batches end in order, after
+# their render.
     def _retire(self, im, delay):
         with self._rlock:
             self._retired.append((self._seq + delay, im))

@@ -3,6 +3,7 @@
 //
 //   Mosaic canvas (four resized sources placed around the mosaic centre, 114 elsewhere; augment.py:657-713)
 //   -> RandomPerspective's cv2.warpAffine (INTER_LINEAR, border 114; augment.py:1016-1077)
+//   -> MixUp with a second such layer (float64 blend, truncated; augment.py:926-948; adr_augment_mix_u8 only)
 //   -> RandomHSV (BGR -> HSV, per-channel LUTs, HSV -> BGR; augment.py:1344-1378)
 //   -> RandomFlip up-down / left-right (index mirrors; augment.py:1429-1472)
 //   -> Format's HWC BGR -> CHW RGB (augment.py:2072-2100) into the collated uint8 (B, 3, H, W) batch
@@ -37,6 +38,12 @@ struct AugDesc {
   int lut_off;      // -1: no HSV; else 768 bytes (hue, sat, val)
   int flip_ud, flip_lr, rgb;
   int pad_;
+};
+
+struct AugMix {
+  int second;  // index into descs of the second layer's descriptor, or -1: the image is not mixed
+  int pad_;
+  double r, one_minus_r;  // both from the host: 1 - r is never recomputed here
 };
 
 namespace {
@@ -102,17 +109,10 @@ __device__ __forceinline__ void hsv2bgr(int hi, int si, int vi, int out[3]) {
   }
 }
 
-}  // namespace
-
-__global__ void __launch_bounds__(256) augment_u8_kernel(const uint8_t* pool, const AugDesc* descs, const int* tabs,
-                                                          const uint8_t* luts, uint8_t* out, int H, int W) {
-  const int b = blockIdx.y;
-  const int p = blockIdx.x * 256 + threadIdx.x;
-  if (p >= H * W) return;
-  const AugDesc& d = descs[b];
-  const int y = p / W, x = p - y * W;
-  const int ys = d.flip_ud ? H - 1 - y : y, xs = d.flip_lr ? W - 1 - x : x;
-  int bgr[3];
+// One layer of the chain at output pixel (xs, ys) (already mirrored): the canvas pixel, or cv::warpAffine's
+// fixed-point bilinear of its four canvas taps, clamped. Shared by the plain and the MixUp kernel.
+__device__ __forceinline__ void layer_px(const uint8_t* pool, const AugDesc& d, const int* tabs, int xs, int ys,
+                                         int H, int W, int bgr[3]) {
   if (d.warp) {
     const int* t = tabs + d.tab_off;
     const int X = (t[2 * W + ys] + t[xs]) >> 5, Y = (t[2 * W + H + ys] + t[W + xs]) >> 5;
@@ -132,6 +132,11 @@ __global__ void __launch_bounds__(256) augment_u8_kernel(const uint8_t* pool, co
   } else {
     canvas_px(pool, d, xs, ys, bgr);
   }
+}
+
+// RandomHSV on the pixel (when the image has LUTs), then the three coalesced plane stores in the image's channel order
+__device__ __forceinline__ void hsv_store(const AugDesc& d, const uint8_t* luts, int bgr[3], uint8_t* out, int b, int p,
+                                          int H, int W) {
   if (d.lut_off >= 0) {
     const uint8_t* L = luts + d.lut_off;
     int h, s, v;
@@ -142,6 +147,52 @@ __global__ void __launch_bounds__(256) augment_u8_kernel(const uint8_t* pool, co
   uint8_t* o = out + (long)b * 3 * plane + p;
 #pragma unroll
   for (int c = 0; c < 3; ++c) o[c * plane] = (uint8_t)bgr[d.rgb ? 2 - c : c];
+}
+
+}  // namespace
+
+__global__ void __launch_bounds__(256) augment_u8_kernel(const uint8_t* pool, const AugDesc* descs, const int* tabs,
+                                                          const uint8_t* luts, uint8_t* out, int H, int W) {
+  const int b = blockIdx.y;
+  const int p = blockIdx.x * 256 + threadIdx.x;
+  if (p >= H * W) return;
+  const AugDesc& d = descs[b];
+  const int y = p / W, x = p - y * W;
+  const int ys = d.flip_ud ? H - 1 - y : y, xs = d.flip_lr ? W - 1 - x : x;
+  int bgr[3];
+  layer_px(pool, d, tabs, xs, ys, H, W, bgr);
+  hsv_store(d, luts, bgr, out, b, p, H, W);
+}
+
+// MixUp (augment.py:926-948) between the warp and RandomHSV: image b's own descriptor gives the first layer, the
+// LUTs, the flips and the channel order; descs[mix[b].second] (second >= 0) gives the second layer's canvas and warp
+// only. The flips act on the blended image, so both layers are read at the same mirrored pixel. The branch is
+// uniform over the block (blockIdx.y).
+__global__ void __launch_bounds__(256) augment_mix_u8_kernel(const uint8_t* pool, const AugDesc* descs,
+                                                              const AugMix* mix, const int* tabs, const uint8_t* luts,
+                                                              uint8_t* out, int H, int W) {
+  const int b = blockIdx.y;
+  const int p = blockIdx.x * 256 + threadIdx.x;
+  if (p >= H * W) return;
+  const AugDesc& d = descs[b];
+  const AugMix& m = mix[b];
+  const int y = p / W, x = p - y * W;
+  const int ys = d.flip_ud ? H - 1 - y : y, xs = d.flip_lr ? W - 1 - x : x;
+  int bgr[3];
+  layer_px(pool, d, tabs, xs, ys, H, W, bgr);
+  if (m.second >= 0) {
+    int b2[3];
+    layer_px(pool, descs[m.second], tabs, xs, ys, H, W, b2);
+    // numpy's (img1 * r + img2 * (1 - r)).astype(np.uint8): two float64 products, each rounded, one float64 sum,
+    // truncation toward zero. It must stay two multiplies and an add (contraction is off for this file): an FMA
+    // skips the rounding of one product and moves the pixels where v * r + v * (1 - r) falls just below v.
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+      const double q0 = (double)bgr[k] * m.r, q1 = (double)b2[k] * m.one_minus_r;
+      bgr[k] = (int)(q0 + q1);
+    }
+  }
+  hsv_store(d, luts, bgr, out, b, p, H, W);
 }
 
 }  // namespace adr
@@ -157,3 +208,20 @@ extern "C" int adr_augment_u8(const void* pool, const void* descs, int B, const 
 }
 
 extern "C" int adr_augment_desc_size(void) { return (int)sizeof(AugDesc); }
+
+extern "C" int adr_augment_mix_u8(const void* pool, const void* descs, int ndesc, const void* mix,
+                                  const void* mix_host, int B, const int* tables, const void* luts, void* out, int H,
+                                  int W, void* stream) {
+  ADR_REQUIRE(B > 0 && H > 0 && W > 0 && (long)H * W < (1l << 30), "augment_mix: B=%d H=%d W=%d", B, H, W);
+  ADR_REQUIRE(ndesc >= B && mix_host != nullptr, "augment_mix: ndesc=%d B=%d mix_host=%p", ndesc, B, mix_host);
+  const AugMix* mh = (const AugMix*)mix_host;
+  for (int b = 0; b < B; ++b)
+    ADR_REQUIRE(mh[b].second == -1 || (mh[b].second >= B && mh[b].second < ndesc),
+                "augment_mix: image %d second=%d outside [%d, %d)", b, mh[b].second, B, ndesc);
+  hipLaunchKernelGGL(augment_mix_u8_kernel, dim3(cdiv((long)H * W, 256), B), dim3(256), 0, (hipStream_t)stream,
+                     (const uint8_t*)pool, (const AugDesc*)descs, (const AugMix*)mix, tables, (const uint8_t*)luts,
+                     (uint8_t*)out, H, W);
+  return check_launch("adr_augment_mix_u8");
+}
+
+extern "C" int adr_augment_mix_desc_size(void) { return (int)sizeof(AugMix); }
