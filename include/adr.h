@@ -602,6 +602,29 @@ int adr_resize_desc_size(void);
  * fp32. Rows r >= counts[b] stay untouched (counts NULL: every row). xywh != 0: columns 2, 3 keep their pad. */
 int adr_scale_boxes(float* boxes, const int* counts, const float* table, int B, int rows, int cols, int xywh,
                     void* stream);
+/* Test-time augmentation views (nn/tasks.py:357-368 _predict_augment's scale_img(x.flip(fi) if fi else x, si, gs);
+ * utils/torch_utils.py:439-448): every non-identity view of the batch img (B, 3, H, W) in one launch. dtype 0: img is
+ * fp32; 1: uint8, x * fp32(1/255) first (the predictor's preprocess, as adr_image_u8_to_nhwc reads it). views:
+ * nviews device adr_tta_view records {int64 out_off; int rh, rw, ph, pw, flip, pad; size adr_tta_view_size()} and views_host the same records
+ * in host memory (validated here: sizes > 0, resized <= padded, pw % 4 == 0, flip 0 / 1, every view's (B, 3, ph, pw)
+ * fp32 batch at the 4-aligned element offset out_off inside out (out_elems floats, 16-byte aligned), no two views
+ * overlapping; any violation returns a non-zero status and launches nothing). Inside (rh, rw) a pixel is
+ * F.interpolate(mode="bilinear", align_corners=False) of the source (read at column W - 1 - x when flip) with ATen's
+ * fp32 arithmetic, uncontracted: scale = (float)in / out; src = max(scale * (dst + 0.5f) - 0.5f, 0); i0 = (int)src;
+ * i1 = i0 + (i0 < in - 1); l1 = src - i0; l0 = 1 - l1; l0h * (l0w * a + l1w * b) + l1h * (l0w * c + l1w * d).
+ * Outside it the pad value 0.447f (:448). The output is NCHW fp32, what adr_stem_conv_fwd / adr_image_to_nhwc read. */
+int adr_tta_views(int dtype, const void* img, int B, int H, int W, const void* views, const void* views_host,
+                  int nviews, void* out, size_t out_elems, void* stream);
+int adr_tta_view_size(void);
+/* Test-time augmentation merge (nn/tasks.py:369-372: _descale_pred :374-383, _clip_augmented :385-394, torch.cat(y,
+ * -1)): the three decoded outputs y_v (B, rows, anchors[v]) fp32 -> out (B, rows, A_total), view v's columns
+ * [keep0[v], keep1[v]) one after the other (A_total is their sum; checked). Rows 0-3 are divided by scales[v] (a true
+ * IEEE fp32 division, as `p[:, :4] /= scale`; a view with scale 1 comes out bit-identical), row 0 of a view with
+ * flips[v] != 0 is then img_w - x (the base image width), rows >= 4 are copied. anchors, keep0, keep1, scales, flips:
+ * host arrays of 3 (read during the call, not after it). */
+int adr_tta_merge(const float* y0, const float* y1, const float* y2, const int* anchors, const int* keep0,
+                  const int* keep1, const float* scales, const int* flips, float img_w, float* out, int B, int rows,
+                  int A_total, void* stream);
 /* W (Cout, C, 3, 3) fp32 -> [(tap*C + c)][Cout] operand for dcols = dy x W. */
 int adr_dcn_weight_t(int dtype, const float* w, void* out, int Cout, int C, void* stream);
 /* Per-image 2-layer gate MLP on pooled vectors: out = act2(W2 act1(W1 (in*in_scale) + b1) + b2);

@@ -22,10 +22,14 @@ class FusedPredictor:
     """predict(img) -> list of (n_i, 6) [x1, y1, x2, y2, conf, cls] tensors, as ops.non_max_suppression returns.
 
     conf / iou / max_det default to the predictor's (cfg/default.yaml: conf 0.25, iou 0.7, max_det 300); pass the
-    validator's conf=0.001, multi_label=True for mAP evaluation."""
+    validator's conf=0.001, multi_label=True for mAP evaluation. augment=True is the reference's test-time
+    augmentation (nn/tasks.py:357-394): three forwards (scale 1, 0.83 left-right flipped, 0.67) merged before the NMS,
+    boxes in the base batch's coordinates — views, forwards, merge and NMS are captured into the one hipGraph."""
 
-    def __init__(self, model, conf=0.25, iou=0.7, max_det=300, agnostic=False, multi_label=False, classes=None):
+    def __init__(self, model, conf=0.25, iou=0.7, max_det=300, agnostic=False, multi_label=False, classes=None,
+                 augment=False):
         self.model = model
+        self.augment = bool(augment)
         self.conf, self.iou, self.max_det = conf, iou, max_det
         self.agnostic, self.multi_label, self.classes = agnostic, multi_label, classes
         self.graph = None
@@ -43,7 +47,7 @@ class FusedPredictor:
     def _run(self, img):
         with torch.no_grad(), K.pack_scope(self.packs):
             first = not self.packs.valid
-            y = self.model(img)
+            y = self.model(img, augment=True) if self.augment else self.model(img)
             if first and self.packs.specs:
                 self.packs.valid = True  # the recording forward packed every operand into the cache
             y = y[0] if isinstance(y, (list, tuple)) else y

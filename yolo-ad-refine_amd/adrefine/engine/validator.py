@@ -34,14 +34,16 @@ class DetectionValidator:
     'confusion_matrix') and 'speed' = {'preprocess', 'inference', 'postprocess'} in ms per image from HIP events
     read after the loop.
 
-    `model` is the validator's own copy of the network (eval mode; load_ema overwrites its weights)."""
+    `model` is the validator's own copy of the network (eval mode; load_ema overwrites its weights). augment=True
+    validates with the reference's test-time augmentation (val(..., augment=True); FusedPredictor(augment=True))."""
 
-    def __init__(self, model, nc, conf=0.001, iou=0.7, max_det=300, agnostic=False, single_cls=False, cm_conf=None):
+    def __init__(self, model, nc, conf=0.001, iou=0.7, max_det=300, agnostic=False, single_cls=False, cm_conf=None,
+                 augment=False):
         self.model, self.nc = model, nc
         self.single_cls = bool(single_cls)
         # val.py:94-102: multi_label=True, agnostic = single_cls or agnostic_nms
         self.predictor = FusedPredictor(model, conf=conf, iou=iou, max_det=max_det,
-                                        agnostic=bool(agnostic or single_cls), multi_label=True)
+                                        agnostic=bool(agnostic or single_cls), multi_label=True, augment=augment)
         self.cm_conf = conf if cm_conf is None else cm_conf  # val.py:83 ConfusionMatrix(conf=args.conf)
         self.stats = None
 

@@ -2685,6 +2685,7 @@ def mlca(y, res, wl, wg, local_weight=0.5, out=None):
 class AxisMeanFn(torch.autograd.Function):
     """Row means over W and column means over H, written as NHWC 'images':
     layout 'ela'   -> (2N, C, L, 1): rows [0,N) hold the H-means (L=H), rows [N,2N) the W-means (needs H == W)
+    layout 'ela2'  -> ((N, C, H, 1), (N, C, W, 1)): the H-means and the W-means as two tensors (any H, W)
     layout 'coord' -> (N, C, H+W, 1): per image rows [0,H) H-means then [H,H+W) W-means (CoordAtt cat)."""
 
     @staticmethod
@@ -2694,10 +2695,14 @@ class AxisMeanFn(torch.autograd.Function):
         dev = x.device
         if layout == "ela":
             if H != W:
-                raise RuntimeError("ELA_HSFPN shares one Conv1d over both axes; this build needs H == W")
+                raise RuntimeError("axis_mean: the stacked 'ela' layout needs H == W (layout 'ela2' otherwise)")
             out = empty_act(2 * N, C, H, 1, x.dtype, dev)
             oh, ohn = out.data_ptr(), H * C
             ow, own = out.data_ptr() + N * H * C * out.element_size(), W * C
+        elif layout == "ela2":
+            out = (empty_act(N, C, H, 1, x.dtype, dev), empty_act(N, C, W, 1, x.dtype, dev))
+            oh, ohn = out[0].data_ptr(), H * C
+            ow, own = out[1].data_ptr(), W * C
         else:
             out = empty_act(N, C, H + W, 1, x.dtype, dev)
             oh, ohn = out.data_ptr(), (H + W) * C
@@ -2709,13 +2714,16 @@ class AxisMeanFn(torch.autograd.Function):
         return out
 
     @staticmethod
-    def backward(ctx, dy):
+    def backward(ctx, dy, dy_w=None):
         layout, shape, dtype = ctx.meta
         N, C, H, W = shape
         dy = dy.contiguous(memory_format=torch.channels_last) if not _is_dense_nhwc(dy) else dy
         es = dy.element_size()
         if layout == "ela":
             dh, dhn, dw, dwn = dy.data_ptr(), H * C, dy.data_ptr() + N * H * C * es, W * C
+        elif layout == "ela2":
+            dy_w = dy_w.contiguous(memory_format=torch.channels_last) if not _is_dense_nhwc(dy_w) else dy_w
+            dh, dhn, dw, dwn = dy.data_ptr(), H * C, dy_w.data_ptr(), W * C
         else:
             dh, dhn, dw, dwn = dy.data_ptr(), (H + W) * C, dy.data_ptr() + H * C * es, (H + W) * C
         dx, acc = _dx_dst(ctx, (N, C, H, W), dtype, dy.device)
@@ -2735,7 +2743,8 @@ def axis_mean(x, layout):
 
 class GateFn(torch.autograd.Function):
     """out = (x if x is not None else 1) * a_h[n,h,c] * a_w[n,w,c], with a = the (.., L, 1) planes produced in
-    the AxisMeanFn layouts ('ela': a is (2N, C, L, 1); 'coord': a_h / a_w are (N, C, H+W, 1) tensors)."""
+    the AxisMeanFn layouts ('ela': a is (2N, C, L, 1); 'ela2': a_h (N, C, H, 1) and a_w (N, C, W, 1); 'coord': a_h /
+    a_w are (N, C, H+W, 1) tensors)."""
 
     @staticmethod
     def forward(ctx, x, ah_t, aw_t, layout, shape):
@@ -2747,6 +2756,9 @@ class GateFn(torch.autograd.Function):
         if layout == "ela":
             ah, ahn = ah_t.data_ptr(), H * C
             aw, awn = aw_t.data_ptr() + N * H * C * es, W * C
+        elif layout == "ela2":
+            ah, ahn = ah_t.data_ptr(), H * C
+            aw, awn = aw_t.data_ptr(), W * C
         else:
             ah, ahn = ah_t.data_ptr(), (H + W) * C
             aw, awn = aw_t.data_ptr() + H * C * es, (H + W) * C
@@ -2773,6 +2785,10 @@ class GateFn(torch.autograd.Function):
             da = torch.empty_like(ah_t, memory_format=torch.channels_last)
             dah, dahn, daw, dawn = da.data_ptr(), H * C, da.data_ptr() + N * H * C * es, W * C
             dah_t = daw_t = None
+        elif layout == "ela2":
+            dah_t = torch.empty_like(ah_t, memory_format=torch.channels_last)
+            daw_t = torch.empty_like(aw_t, memory_format=torch.channels_last)
+            dah, dahn, daw, dawn = dah_t.data_ptr(), H * C, daw_t.data_ptr(), W * C
         else:
             # the kernel zeroes the rows the gate does not use (dah rows H.., daw rows ..H): no fill launches
             dah_t = torch.empty_like(ah_t, memory_format=torch.channels_last)
@@ -2783,7 +2799,7 @@ class GateFn(torch.autograd.Function):
         vx = _v(x) if has_x else (None, 0, 0)
         _gate_bwd(dcode(dtype), vx[1] if has_x else None, vx[2], ah, ahn, aw, awn, vd[1], vd[2],
                   dx.data_ptr() if has_x else None, dx.stride(3) if has_x else C, dah, dahn, daw, dawn, N, H, W, C,
-                  acc, int(layout != "ela"), dout.device)
+                  acc, int(layout == "coord"), dout.device)
         if ctx.sink is not None:
             dx = None
         if layout == "ela":

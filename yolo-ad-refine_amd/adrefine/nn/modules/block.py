@@ -198,8 +198,12 @@ class ELA_HSFPN(nn.Module):  # noqa: N801 (reference name)
         conv, gn = self.conv1x1[0], self.conv1x1[1]
         if self.flag:
             x, xg = K.fanout(x)
-        p = K.axis_mean(x, "ela")  # (2N, C, L, 1): both branches as separate "images" (GN per branch)
         w4 = conv.weight.unsqueeze(-1)  # (C, C, 7) -> (C, C, 7, 1): a 7x1 conv over the pooled axis
+        if H != W:  # the axes differ in length (rectangular batches, the scaled test-time views): a batch per branch
+            a_h, a_w = (K.gn_act(K.conv2d(p, w4, conv.bias, (1, 1), (3, 0))[0], gn, "sigmoid")
+                        for p in K.axis_mean(x, "ela2"))
+            return K.gate(xg if self.flag else None, a_h, a_w, "ela2", x.shape)
+        p = K.axis_mean(x, "ela")  # (2N, C, L, 1): both branches as separate "images" (GN per branch)
         y, _ = K.conv2d(p, w4, conv.bias, (1, 1), (3, 0))
         a = K.gn_act(y, gn, "sigmoid")
         return K.gate(xg if self.flag else None, a, a, "ela", x.shape)

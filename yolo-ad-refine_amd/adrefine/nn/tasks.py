@@ -305,7 +305,26 @@ class DetectionModel(nn.Module):
         return self.predict(x, *args, **kwargs)
 
     def predict(self, x, profile=False, visualize=False, augment=False, embed=None, cuts=()):
+        if augment:
+            return self._predict_augment(x)
         return self._predict_once(x, cuts)
+
+    def _predict_augment(self, x):
+        """tasks.py:357-372: three eval forwards (scale 1, scale 0.83 of the left-right flipped batch, scale 0.67),
+        each de-scaled and de-flipped, the tails clipped, concatenated along the anchor axis -> (y_cat, None). The
+        views are one adr_tta_views launch, the merge one adr_tta_merge launch (utils/tta.py)."""
+        from ..utils.tta import tta_merge, tta_plan, tta_views
+        if self.training:
+            raise RuntimeError("predict(augment=True) is an inference path: call model.eval() first")
+        m = self.model[-1]
+        if not isinstance(m, (head.Detect, head.AYHead1)):
+            raise NotImplementedError("predict(augment=True) needs a detection head")
+        plan = tta_plan(x.shape[2], x.shape[3], gs=int(self.stride.max()), nl=m.nl)
+        ys = []
+        for xi in tta_views(x, plan):
+            yi = self._predict_once(xi)
+            ys.append(yi[0] if isinstance(yi, (list, tuple)) else yi)
+        return tta_merge(ys, plan), None
 
     def _predict_once(self, x, cuts=()):
         """tasks.py:141-168 layer routing by m.f with the save list. `cuts` (layer indices) splits the autograd
