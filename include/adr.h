@@ -677,6 +677,17 @@ int adr_dwconv_wgrad_bias_fusable(int dtype, int H, int W, int C, int k, int xcs
 int adr_dwconv_wgrad_partials_bias(int dtype, const void* x, int xcs, const void* dy, int dcs, int N, int H, int W,
                                    int C, int k, float* ws, size_t ws_bytes, float* bias_part, int* chunks,
                                    void* stream);
+/* The whole depthwise backward in one launch per (image, 8-channel slab): x and dy are staged once, then dx (+)= the
+ * data gradient, the weight gradient's partial rows ([*chunks = N][k*k][C] floats in ws) and, with bias_part, the bias
+ * rows ([N][2][C], half 0), each bitwise what adr_dwconv_bwd and adr_dwconv_wgrad_partials[_bias] write in two
+ * launches. dw non-NULL: the partial rows are reduced into dw at once (dw_accumulate as in adr_dwconv_bwd). Only where
+ * adr_dwconv_bwd_fused_supported says so (bf16, k in {3, 5, 7}, both fp32 images within 64 KB of LDS: the 20x20
+ * maps; ADR_DW_FUSED=0 switches it off). Reference: the backward of nn.Conv2d(groups=C) in ProgressiveFeatureFusion
+ * (block.py:2589-2593) and EDFFN (:2387). */
+int adr_dwconv_bwd_fused_supported(int dtype, int H, int W, int C, int k, int xcs, int dcs, int ocs);
+int adr_dwconv_bwd_fused(int dtype, const void* x, int xcs, const void* dy, int dcs, const float* w, void* dx, int ocs,
+                         float* dw, int N, int H, int W, int C, int k, int accumulate, int dw_accumulate, float* ws,
+                         size_t ws_bytes, float* bias_part, int* chunks, void* stream);
 /* AdaptiveDynamicTanh (:2493-2577): y = (sum_i tanh(alpha_i x) imp[n,i]) * w[c] + b[c]; imp from adr_gate_mlp. */
 int adr_adyt_fwd(int dtype, const void* x, int xcs, const float* alphas, const float* imp, const float* w,
                  const float* b, void* y, int ycs, int N, int HW, int C, void* stream);

@@ -120,6 +120,11 @@ _ALG_BYTES = {
                        lambda a: _es(a[0]) * a[11] * a[12] * a[13] * 2, lambda a: True),
     "adr_nc_reduce": (lambda a: f"adr::nc_reduce_kernel<__bf16, {1 if a[1] == 1 else 0}, {a[11] if a[1] == 1 else 0}>",
                       lambda a: _es(a[0]) * a[12] * a[13] * a[14] * (2 if a[1] == 1 else 1), lambda a: True),
+    # the one-launch depthwise backward: x, dy read, dx written (read too when accumulating), the partial rows written
+    "adr_dwconv_bwd_fused": (lambda a: f"adr::dw_bwd_fused_kernel<__bf16, {a[13]}>",
+                             lambda a: _es(a[0]) * a[9] * a[10] * a[11] * a[12] * (3 + a[14])
+                             + 4 * a[12] * a[13] * a[13] * (a[9] + 1),
+                             lambda a: a[14] == 0 and not (_ptr(a[8]) and a[15])),
     "adr_ew": ("adr::ew_kernel<__bf16>",
                lambda a: _es(a[0]) * a[11] * a[12] * (2 + (a[5] is not None) + (a[7] is not None) + a[15]),
                lambda a: a[15] == 0 and _ptr(a[9]) not in (_ptr(a[3]), _ptr(a[5]), _ptr(a[7]))),
@@ -3240,6 +3245,24 @@ class DWConvFn(torch.autograd.Function):
         # weight gradient into the arena: the partial rows now, their reduction batched at the deferred flush
         # (adr_wgrad_reduce_batched with K = 1, RS = k*k: the [C][k*k] parameter layout)
         defer = pdw is not None and dacc and _dfr() is not None and _TIMING is None and wsb <= DEFER_MAX_BYTES
+        if (dx is not None and pdw is not None and
+                lib.adr_dwconv_bwd_fused_supported(dcode(x.dtype), H, W, C, k, vx[2], vd[2], dx.stride(3))):
+            # one launch: dx, the weight gradient's partial rows and (where the two-launch path fuses them) the bias rows
+            bpart = None
+            if (defer and has_b and ctx.needs_input_grad[2] and _fuse_wg_bias() and
+                    lib.adr_dwconv_wgrad_bias_fusable(dcode(x.dtype), H, W, C, k, vx[2], vd[2])):
+                bpart = torch.empty(N * 2 * C, dtype=torch.float32, device=x.device)
+            chunks = ctypes.c_int(0)
+            lib.adr_dwconv_bwd_fused(dcode(x.dtype), ctypes.c_void_p(vx[1]), vx[2], ctypes.c_void_p(vd[1]), vd[2],
+                                     fptr(wf), ctypes.c_void_p(dx.data_ptr()), dx.stride(3), None if defer else pdw,
+                                     N, H, W, C, k, acc, dacc, fptr(ws), wsb, fptr(bpart), ctypes.byref(chunks),
+                                     stream())
+            db = _bias_rows(ctx.pb, C, N, bpart, x.device) if bpart is not None else None
+            if defer:
+                _dfr().add(ws, k * k * C, chunks.value, pdw, 1, C, C, k * k, 0, dacc)
+            if has_b and ctx.needs_input_grad[2] and bpart is None:
+                db = _bias_grad(vd[0], C, N, H * W, vd[2], ctx.pb)
+            return (None if ctx.sink is not None else dx), grad_ret(ctx.pw, dw), db, None
         lib.adr_dwconv_bwd(dcode(x.dtype), ctypes.c_void_p(vx[1]), vx[2], ctypes.c_void_p(vd[1]), vd[2], fptr(wf),
                            ctypes.c_void_p(dx.data_ptr()) if dx is not None else None,
                            dx.stride(3) if dx is not None else C, None if defer else pdw, N, H, W, C, k, acc, dacc,

@@ -156,10 +156,11 @@ __device__ __forceinline__ void stage_img(const T* src, int cs, int H, int W, in
   }
 }
 
-// the padded image staged as fp32 in LDS (converted once, not per tap read): CB channels per pixel row
+// the padded image staged as fp32 in LDS (converted once, not per tap read): CB channels per pixel row; rs: the LDS
+// row stride in pixels (0: the padded width, rows packed)
 template <typename T, int CBT>
 __device__ __forceinline__ void stage_img_f32(const T* src, int cs, int H, int W, int pad, int cb0, int C, int CB,
-                                              float* dst) {
+                                              float* dst, int rs = 0) {
   constexpr int VW = (int)(16 / sizeof(T)) < CBT ? (int)(16 / sizeof(T)) : CBT;  // a 4-channel slab: 8-byte bf16 reads
   constexpr int U = 8;  // loads in flight per thread
   const int Hp = H + 2 * pad, Wp = W + 2 * pad, nv = CB / VW, tot = Hp * Wp * nv;
@@ -179,7 +180,8 @@ __device__ __forceinline__ void stage_img_f32(const T* src, int cs, int H, int W
     for (int u = 0; u < U; ++u) {
       const int i = i0 + u * blockDim.x;
       if (i >= tot) continue;
-      float* d = dst + (long)(i / nv) * CB + (i % nv) * VW;
+      const int pp = i / nv;
+      float* d = dst + (long)(rs ? (pp / Wp) * rs + pp % Wp : pp) * CB + (i % nv) * VW;
 #pragma unroll
       for (int e = 0; e < VW; e += 4)
         *reinterpret_cast<f32x4*>(d + e) = (f32x4){f[u][e], f[u][e + 1], f[u][e + 2], f[u][e + 3]};
@@ -192,7 +194,9 @@ __device__ __forceinline__ void stage_img_f32(const T* src, int cs, int H, int W
 // the bias, and the activation is applied before the store — the reference's fuse_conv_and_bn on a depthwise conv.
 // F32S (bf16 tensors whose fp32 padded slab fits the LDS plan): the image is converted to fp32 once at staging, so a
 // tap is two 16-byte LDS reads + four v_pk_fma_f32 per 8 channels instead of eight conversions + eight FMAs — the
-// kernel is VALU-bound (a 7x7 at 20x20: 27 us at ~12 TF/s). Per output the sum is bias + taps in (ky, kx) order,
+// kernel was taken for VALU-bound (a 7x7 at 20x20: 27 us at ~12 TF/s); its counters show the LDS array busy most of
+// the launch, 47 % of that in bank conflicts (profiles/r07a_dw_micro.md): the bf16 20x20 maps now run dw_run_kernel
+// below, this body serves the rest. Per output the sum is bias + taps in (ky, kx) order,
 // each an fp32 fma: bitwise the same for every variant.
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 template <typename T, bool BWD, int CB, bool EPI, bool F32S = false>
@@ -314,13 +318,18 @@ __global__ void __launch_bounds__(256) dw_img_act_kernel(const __bf16* x, int xc
 
 // the depthwise conv's bias gradient for this (image, channel slab): column sums of the staged fp32 dy image,
 // CB channels x (256 / CB) pixel splits combined in a fixed order; bias_part[n][2][C], half 0
+// (W > 0: ds is the interior of a padded image with rows of rs pixels; the same pixels in the same order)
 template <int CB>
-__device__ __forceinline__ void dw_bias_rows(const float* ds, int HW, int n, int cb0, int C, float* bias_part) {
+__device__ __forceinline__ void dw_bias_rows(const float* ds, int HW, int n, int cb0, int C, float* bias_part,
+                                             int W = 0, int rs = 0) {
   __shared__ float bred[256];
   constexpr int PSPL = 256 / CB;
   const int c = threadIdx.x % CB, ps = threadIdx.x / CB;
   float sacc = 0.f;
-  for (int pix = ps; pix < HW; pix += PSPL) sacc += ds[(long)pix * CB + c];
+  if (W > 0)
+    for (int pix = ps; pix < HW; pix += PSPL) sacc += ds[((long)(pix / W) * rs + pix % W) * CB + c];
+  else
+    for (int pix = ps; pix < HW; pix += PSPL) sacc += ds[(long)pix * CB + c];
   bred[threadIdx.x] = sacc;
   __syncthreads();
   if (threadIdx.x < CB) {
@@ -390,19 +399,11 @@ __global__ void __launch_bounds__(256) dw_wgrad_img_kernel(const T* x, int xcs, 
 // split rs) walks whole output rows; per pixel it loads ONE dy vector and ONE new padded-x vector (the previous
 // k - 1 stay in registers) for k taps, instead of two LDS loads per tap. The RS row splits of an item are adjacent
 // lanes of one wave, combined by an xor butterfly (fixed order: deterministic).
-template <typename T, int CB, int KS>
-__global__ void __launch_bounds__(256) dw_wgrad_row_kernel(const T* x, int xcs, const T* dy, int dcs, int H, int W,
-                                                           int C, float* partial, float* bias_part) {
-  constexpr int NV = CB / 4, P = KS / 2, KK = KS * KS;
-  extern __shared__ __attribute__((aligned(16))) unsigned char dwsm[];
-  const int n = blockIdx.x, cb0 = blockIdx.y * CB;
-  const int Hp = H + 2 * P, Wp = W + 2 * P;
-  float* xs = reinterpret_cast<float*>(dwsm);
-  float* ds = xs + (long)Hp * Wp * CB;
-  stage_img_f32<T, CB>(x + (long)n * H * W * xcs, xcs, H, W, P, cb0, C, CB, xs);
-  stage_img_f32<T, CB>(dy + (long)n * H * W * dcs, dcs, H, W, 0, cb0, C, CB, ds);
-  __syncthreads();
-  if (bias_part) dw_bias_rows<CB>(ds, H * W, n, cb0, C, bias_part);
+template <int CB, int KS>
+__device__ __forceinline__ void dw_wgrad_row_body(const float* xs, int xrs, const float* ds, int drs, int n, int cb0,
+                                                  int H, int W, int C, float* partial) {
+  // xs: the image padded by KS / 2, rows of xrs pixels; ds: dy's pixel (0, 0), rows of drs pixels
+  constexpr int NV = CB / 4, KK = KS * KS;
   constexpr int pairs = KS * NV;
   int RS = 1;  // row splits per (ky, group): a power of two <= 64 dividing 256, so a group sits in one wave
   while (RS * 2 * pairs <= 256 && RS < 64 && RS < H) RS *= 2;
@@ -415,8 +416,8 @@ __global__ void __launch_bounds__(256) dw_wgrad_row_kernel(const T* x, int xcs, 
     if (pr < pairs) {
       const int ky = pr / NV, cv = pr % NV;
       for (int oy = rs; oy < H; oy += RS) {
-        const float* xr = xs + (long)(oy + ky) * Wp * CB + cv * 4;
-        const float* dr = ds + (long)oy * W * CB + cv * 4;
+        const float* xr = xs + (long)(oy + ky) * xrs * CB + cv * 4;
+        const float* dr = ds + (long)oy * drs * CB + cv * 4;
         f32x4 xw[KS];
 #pragma unroll
         for (int kx = 0; kx < KS - 1; ++kx) xw[kx] = *reinterpret_cast<const f32x4*>(xr + kx * CB);
@@ -444,6 +445,137 @@ __global__ void __launch_bounds__(256) dw_wgrad_row_kernel(const T* x, int xcs, 
           if (c + e < C) partial[((long)n * KK + ky * KS + kx) * C + c + e] = acc[kx][e];
     }
   }
+}
+
+template <typename T, int CB, int KS>
+__global__ void __launch_bounds__(256) dw_wgrad_row_kernel(const T* x, int xcs, const T* dy, int dcs, int H, int W,
+                                                           int C, float* partial, float* bias_part) {
+  constexpr int P = KS / 2;
+  extern __shared__ __attribute__((aligned(16))) unsigned char dwsm[];
+  const int n = blockIdx.x, cb0 = blockIdx.y * CB;
+  const int Hp = H + 2 * P, Wp = W + 2 * P;
+  float* xs = reinterpret_cast<float*>(dwsm);
+  float* ds = xs + (long)Hp * Wp * CB;
+  stage_img_f32<T, CB>(x + (long)n * H * W * xcs, xcs, H, W, P, cb0, C, CB, xs);
+  stage_img_f32<T, CB>(dy + (long)n * H * W * dcs, dcs, H, W, 0, cb0, C, CB, ds);
+  __syncthreads();
+  if (bias_part) dw_bias_rows<CB>(ds, H * W, n, cb0, C, bias_part);
+  dw_wgrad_row_body<CB, KS>(xs, Wp, ds, W, n, cb0, H, W, C, partial);
+}
+
+// ---- row-run forward / data gradient, and the one-launch backward ----
+// An item is a run of DW_RUN_R consecutive output pixels of one row x one 4-channel vector of the block's 8-channel
+// slab. Per ky it loads the KS tap vectors of that tap row and the R + KS - 1 staged pixels under the run once and
+// applies the R x KS fmas from registers: (R + 2 KS - 1) / R 16-byte LDS reads per output pixel and ky instead of the
+// 2 KS of dw_img_body (k = 7: 4.25 against 14). Per output the sum is still bias, then the taps in (ky, kx) order, each
+// one fp32 fma on the same operands: bitwise dw_img_body's result (forward, mirrored taps, accumulate).
+// LDS rows are padded to an odd pixel count and items run down the columns (oy fastest), so the eight runs of a
+// ds_read_b128 lane group sit at eight different 32-byte bank slots.
+typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
+constexpr int DW_RUN_R = 4, DW_RUN_CB = 8;
+template <typename T, bool BWD, int KS>
+__device__ __forceinline__ void dw_run_items(const float* img, int rs, const float* wl, const float* b, T* y, int ycs,
+                                             int H, int W, int accumulate) {
+  // img: the image padded by KS / 2, rows of rs pixels of CB floats; wl: [KS * KS][CB]; b, y: at the slab's channel 0
+  static_assert(sizeof(T) == 2, "dw_run_items: 4 channels are one 8-byte store");
+  constexpr int R = DW_RUN_R, CB = DW_RUN_CB, NX = R + KS - 1;
+  const int rpr = (W + R - 1) / R, total = rpr * H * (CB / 4);
+  for (int it = threadIdx.x; it < total; it += 256) {
+    const int cv = it % (CB / 4), run = it / (CB / 4);
+    const int oy = run % H, ox0 = (run / H) * R;
+    f32x2 acc[R][2];
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+      acc[r][0] = (!BWD && b) ? (f32x2){b[cv * 4], b[cv * 4 + 1]} : (f32x2){0.f, 0.f};
+      acc[r][1] = (!BWD && b) ? (f32x2){b[cv * 4 + 2], b[cv * 4 + 3]} : (f32x2){0.f, 0.f};
+    }
+#pragma unroll 1  // unrolled, the tap rows' loads are all hoisted: 256 VGPRs and spills at k = 7
+    for (int ky = 0; ky < KS; ++ky) {
+      // forward: x[oy + ky - p][ox + kx - p] = padded (oy + ky, ox + kx); data gradient: taps mirrored (from 2p)
+      const float* xr = img + ((long)(BWD ? oy + KS - 1 - ky : oy + ky) * rs + ox0) * CB + cv * 4;
+      const float* wr = wl + ky * KS * CB + cv * 4;
+      f32x4 xv[NX], wv[KS];
+#pragma unroll
+      for (int j = 0; j < NX; ++j) xv[j] = *reinterpret_cast<const f32x4*>(xr + j * CB);
+#pragma unroll
+      for (int kx = 0; kx < KS; ++kx) wv[kx] = *reinterpret_cast<const f32x4*>(wr + kx * CB);
+#pragma unroll
+      for (int kx = 0; kx < KS; ++kx)
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+          const f32x4 x4 = xv[BWD ? r + KS - 1 - kx : r + kx];
+          acc[r][0] = __builtin_elementwise_fma((f32x2){x4[0], x4[1]}, (f32x2){wv[kx][0], wv[kx][1]}, acc[r][0]);
+          acc[r][1] = __builtin_elementwise_fma((f32x2){x4[2], x4[3]}, (f32x2){wv[kx][2], wv[kx][3]}, acc[r][1]);
+        }
+    }
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+      if (ox0 + r >= W) continue;  // the short last run of a ragged row
+      float a[4] = {acc[r][0][0], acc[r][0][1], acc[r][1][0], acc[r][1][1]};
+      T* dst = y + ((long)oy * W + ox0 + r) * ycs + cv * 4;
+      if (BWD && accumulate) {
+        const u32x2 pv = *reinterpret_cast<const u32x2*>(dst);
+        const T* pe = reinterpret_cast<const T*>(&pv);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) a[e] += to_f(pe[e]);
+      }
+      u32x2 o;
+      T* oe = reinterpret_cast<T*>(&o);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) oe[e] = from_f<T>(a[e]);
+      *reinterpret_cast<u32x2*>(dst) = o;
+    }
+  }
+}
+
+// the taps of the block's slab, tap-major [KS * KS][CB] (dw_img_body's layout)
+template <int KS>
+__device__ __forceinline__ void dw_run_taps(const float* w, int cb0, int C, float* wl) {
+  constexpr int CB = DW_RUN_CB, KK = KS * KS;
+  for (int i = threadIdx.x; i < KK * CB; i += 256) {
+    const int t = i / CB, c = cb0 + i % CB;
+    wl[i] = c < C ? w[(long)c * KK + t] : 0.f;
+  }
+}
+
+// LDS: taps | padded image (rows of rs = (W + 2p) | 1 pixels) | R pixels of slack (the last run of a ragged row reads
+// up to R - 1 pixels past its row; those outputs are not stored)
+template <typename T, bool BWD, int KS>
+__global__ void __launch_bounds__(256) dw_run_kernel(const T* x, int xcs, const float* w, const float* b, T* y,
+                                                     int ycs, int H, int W, int C, int accumulate) {
+  constexpr int CB = DW_RUN_CB, P = KS / 2;
+  extern __shared__ __attribute__((aligned(16))) unsigned char dwsm[];
+  const int n = blockIdx.x, cb0 = blockIdx.y * CB, rs = (W + 2 * P) | 1;
+  float* wl = reinterpret_cast<float*>(dwsm);
+  float* xs = wl + KS * KS * CB;
+  dw_run_taps<KS>(w, cb0, C, wl);
+  stage_img_f32<T, CB>(x + (long)n * H * W * xcs, xcs, H, W, P, cb0, C, CB, xs, rs);
+  __syncthreads();
+  dw_run_items<T, BWD, KS>(xs, rs, wl, b ? b + cb0 : nullptr, y + (long)n * H * W * ycs + cb0, ycs, H, W, accumulate);
+}
+
+// One backward launch per (image, 8-channel slab): x and dy staged once (both padded by p, fp32), then dx by the
+// row-run body over dy, the weight-gradient partial row by the sliding-window body and, when asked, the bias rows:
+// each bitwise what dw_img_kernel<BWD> and dw_wgrad_row_kernel write.
+// LDS: taps | x image | dy image | R pixels of slack
+template <typename T, int KS>
+__global__ void __launch_bounds__(256) dw_bwd_fused_kernel(const T* x, int xcs, const T* dy, int dcs, const float* w,
+                                                           T* dx, int ocs, int H, int W, int C, int accumulate,
+                                                           float* partial, float* bias_part) {
+  constexpr int CB = DW_RUN_CB, P = KS / 2;
+  extern __shared__ __attribute__((aligned(16))) unsigned char dwsm[];
+  const int n = blockIdx.x, cb0 = blockIdx.y * CB, Hp = H + 2 * P, rs = (W + 2 * P) | 1;
+  float* wl = reinterpret_cast<float*>(dwsm);
+  float* xs = wl + KS * KS * CB;
+  float* ds = xs + (long)Hp * rs * CB;
+  dw_run_taps<KS>(w, cb0, C, wl);
+  stage_img_f32<T, CB>(x + (long)n * H * W * xcs, xcs, H, W, P, cb0, C, CB, xs, rs);
+  stage_img_f32<T, CB>(dy + (long)n * H * W * dcs, dcs, H, W, P, cb0, C, CB, ds, rs);
+  __syncthreads();
+  const float* d0 = ds + ((long)P * rs + P) * CB;  // dy's pixel (0, 0)
+  if (bias_part) dw_bias_rows<CB>(d0, H * W, n, cb0, C, bias_part, W, rs);
+  dw_run_items<T, true, KS>(ds, rs, wl, nullptr, dx + (long)n * H * W * ocs + cb0, ocs, H, W, accumulate);
+  dw_wgrad_row_body<CB, KS>(xs, rs, d0, rs, n, cb0, H, W, C, partial);
 }
 
 // dw[c][t] = sum_chunks partial[chunk][t][c]; threads walk c fastest (coalesced partial rows), 8 chunks in flight
@@ -1373,6 +1505,38 @@ static void dw_img_launch(int dtype, hipStream_t st, const void* x, int xcs, con
                        (const float*)x, xcs, w, b, (float*)y, ycs, H, W, C, k, acc);
 }
 
+// ADR_DW_RUN=0: dw_img_kernel instead of the row-run forward / data gradient; ADR_DW_FUSED=0: the data gradient and
+// the weight gradient as two launches. Read per call, so a test can switch them in-process.
+static bool dw_env_on(const char* name) {
+  const char* e = getenv(name);
+  return e ? atoi(e) != 0 : true;
+}
+static size_t dw_run_smem(int H, int W, int k, int images) {
+  const int p = k / 2, rs = (W + 2 * p) | 1;
+  return ((size_t)k * k + (size_t)images * (H + 2 * p) * rs + DW_RUN_R) * DW_RUN_CB * sizeof(float);
+}
+// The row-run kernel serves the shape class it was measured on: bf16 maps that dw_img_launch runs as F32S (the 20x20
+// C2PTSSA / EDFFN maps), k in {3, 5, 7}. Everything else keeps dw_img_kernel.
+static bool dw_run_shape(int dtype, int H, int W, int C, int k) {
+  return dtype == ADR_BF16 && (k == 3 || k == 5 || k == 7) && C % DW_RUN_CB == 0 && dw_img_ok() &&
+         dw_f32s(dtype, H, W, k, dw_fwd_cb(dtype, H, W, k));
+}
+template <bool BWD>
+static bool dw_run_launch(int dtype, hipStream_t st, const void* x, int xcs, const float* w, const float* b, void* y,
+                          int ycs, int N, int H, int W, int C, int k, int acc) {
+  if (!(dw_env_on("ADR_DW_RUN") && dw_run_shape(dtype, H, W, C, k) && xcs % 8 == 0 && ycs % 8 == 0)) return false;
+  const dim3 g(N, C / DW_RUN_CB);
+  const size_t sm = dw_run_smem(H, W, k, 1);
+#define ADR_DWRUN(KS)                                                                                              \
+  hipLaunchKernelGGL((dw_run_kernel<__bf16, BWD, KS>), g, dim3(256), sm, st, (const __bf16*)x, xcs, w, b, (__bf16*)y, \
+                     ycs, H, W, C, acc)
+  if (k == 3) ADR_DWRUN(3);
+  else if (k == 5) ADR_DWRUN(5);
+  else ADR_DWRUN(7);
+#undef ADR_DWRUN
+  return true;
+}
+
 template <typename T, bool BWD>
 static void dw_launch(int k, dim3 grid, size_t sm, hipStream_t st, const T* x, int xcs, const float* w, const float* b,
                       T* y, int ycs, int N, int H, int W, int C, int acc) {
@@ -1394,7 +1558,8 @@ extern "C" int adr_dwconv_fwd(int dtype, const void* x, int xcs, const float* w,
   long total = (long)N * H * W * (C / v);
   size_t sm = (size_t)k * k * C * sizeof(float);
   ADR_REQUIRE(total < (1l << 32) && sm <= 64 * 1024, "dwconv: N*H*W*C=%ld / k=%d C=%d too large", total, k, C);
-  if (dw_img_ok() && dw_fwd_cb(dtype, H, W, k) && xcs % v == 0 && ycs % v == 0) {
+  if (dw_run_launch<false>(dtype, st, x, xcs, w, b, y, ycs, N, H, W, C, k, 0)) {
+  } else if (dw_img_ok() && dw_fwd_cb(dtype, H, W, k) && xcs % v == 0 && ycs % v == 0) {
     dw_img_launch<false>(dtype, st, x, xcs, w, b, y, ycs, N, H, W, C, k, 0);
   } else if (dtype == ADR_BF16)
     dw_launch<__bf16, false>(k, dim3(cdiv(total, 256)), sm, st, (const __bf16*)x, xcs, w, b, (__bf16*)y, ycs, N, H, W,
@@ -1492,7 +1657,8 @@ extern "C" int adr_dwconv_bwd(int dtype, const void* x, int xcs, const void* dy,
   if (dx) {
     size_t sm = (size_t)k * k * C * sizeof(float);
     ADR_REQUIRE(total < (1l << 32) && sm <= 64 * 1024, "dwconv_bwd: N*H*W*C=%ld / k=%d C=%d too large", total, k, C);
-    if (dw_img_ok() && dw_fwd_cb(dtype, H, W, k) && dcs % v == 0 && ocs % v == 0)
+    if (dw_run_launch<true>(dtype, st, dy, dcs, w, nullptr, dx, ocs, N, H, W, C, k, accumulate)) {
+    } else if (dw_img_ok() && dw_fwd_cb(dtype, H, W, k) && dcs % v == 0 && ocs % v == 0)
       dw_img_launch<true>(dtype, st, dy, dcs, w, nullptr, dx, ocs, N, H, W, C, k, accumulate);
     else if (dtype == ADR_BF16)
       dw_launch<__bf16, true>(k, dim3(cdiv(total, 256)), sm, st, (const __bf16*)dy, dcs, w, nullptr, (__bf16*)dx, ocs, N,
@@ -1534,6 +1700,40 @@ extern "C" int adr_dwconv_wgrad_partials_bias(int dtype, const void* x, int xcs,
   ADR_REQUIRE(ws_bytes >= adr_dwconv_wgrad_workspace(N, H, W, C, k), "dwconv_wgrad_partials_bias: workspace");
   *chunks = dw_wgrad_partials(dtype, x, xcs, dy, dcs, N, H, W, C, k, ws, (hipStream_t)stream, bias_part);
   return check_launch("adr_dwconv_wgrad_partials_bias");
+}
+
+// The one-launch backward serves the row-run shape class when both fp32 images fit the LDS plan and the two-launch
+// path would run the sliding-window weight gradient on 8-channel slabs (the same partial sums, bit for bit).
+extern "C" int adr_dwconv_bwd_fused_supported(int dtype, int H, int W, int C, int k, int xcs, int dcs, int ocs) {
+  return dw_env_on("ADR_DW_FUSED") && dw_run_shape(dtype, H, W, C, k) && dw_row_ok() && xcs % 8 == 0 &&
+                 dcs % 8 == 0 && ocs % 8 == 0 && C / 8 <= 256 && dw_wg_cb(H, W, k) == DW_CB_WG &&
+                 dw_run_smem(H, W, k, 2) + 256 * sizeof(float) <= DW_LDS_MAX
+             ? 1
+             : 0;
+}
+
+extern "C" int adr_dwconv_bwd_fused(int dtype, const void* x, int xcs, const void* dy, int dcs, const float* w,
+                                    void* dx, int ocs, float* dw, int N, int H, int W, int C, int k, int accumulate,
+                                    int dw_accumulate, float* ws, size_t ws_bytes, float* bias_part, int* chunks,
+                                    void* stream) {
+  ADR_REQUIRE(x && dy && w && dx && ws && chunks && adr_dwconv_bwd_fused_supported(dtype, H, W, C, k, xcs, dcs, ocs),
+              "dwconv_bwd_fused: H=%d W=%d C=%d k=%d not on the one-launch backward", H, W, C, k);
+  ADR_REQUIRE(ws_bytes >= adr_dwconv_wgrad_workspace(N, H, W, C, k), "dwconv_bwd_fused: workspace");
+  hipStream_t st = (hipStream_t)stream;
+  const dim3 g(N, C / DW_RUN_CB);
+  const size_t sm = dw_run_smem(H, W, k, 2);
+#define ADR_DWFUSED(KS)                                                                                          \
+  hipLaunchKernelGGL((dw_bwd_fused_kernel<__bf16, KS>), g, dim3(256), sm, st, (const __bf16*)x, xcs,             \
+                     (const __bf16*)dy, dcs, w, (__bf16*)dx, ocs, H, W, C, accumulate, ws, bias_part)
+  if (k == 3) ADR_DWFUSED(3);
+  else if (k == 5) ADR_DWFUSED(5);
+  else ADR_DWFUSED(7);
+#undef ADR_DWFUSED
+  *chunks = N;
+  if (dw)
+    hipLaunchKernelGGL(dw_w_reduce_kernel, dim3(cdiv(C * k * k, 256)), dim3(256), 0, st, ws, N, C, k * k, dw,
+                       dw_accumulate);
+  return check_launch("adr_dwconv_bwd_fused");
 }
 
 extern "C" int adr_adyt_fwd(int dtype, const void* x, int xcs, const float* alphas, const float* imp, const float* w,
