@@ -1,5 +1,5 @@
 """Time the DCN forward / backward at the AYHead shapes (bs 64, 64 -> 64 channels, 80/40/20 maps, bf16) with HIP
-events; ADR_DCN_FUSED=0 selects the im2col + GEMM + col2im path for an A/B. Env N, C, SIZES (e.g. N=16 C=256
+events. Env N, C, SIZES (e.g. N=16 C=256
 SIZES=160,80,40 for the l-scale head at 1280), SPREAD (offset range in px)."""
 import os
 import sys

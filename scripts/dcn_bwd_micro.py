@@ -1,5 +1,4 @@
-"""Time adr_dcn_bwd_bf16 alone (HIP events) at one AYHead shape. Env: N, C, S (map side), SPREAD (offset px),
-ADR_DCN_BWD_MODE (1 / 2: skip the dom / dx phase, A/B only)."""
+"""Time adr_dcn_bwd_bf16 alone (HIP events) at one AYHead shape. Env: N, C, S (map side), SPREAD (offset px)."""
 import os
 import sys
 from pathlib import Path
@@ -35,5 +34,5 @@ for _ in range(R):
     run()
 e1.record()
 torch.cuda.synchronize()
-print(f"dcn_bwd N{N} C{C} {S}x{S} spread {spread} mode {os.environ.get('ADR_DCN_BWD_MODE', '0')}: "
+print(f"dcn_bwd N{N} C{C} {S}x{S} spread {spread}: "
       f"{e0.elapsed_time(e1) / R * 1000:.1f} us/launch pair", flush=True)

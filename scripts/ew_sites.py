@@ -34,17 +34,9 @@ for _ in range(2):
     tr.step(batch)
 torch.cuda.synchronize()
 K.TIMING_REPEAT = 1
-K.FANOUT_LOG = []
 K.timing_begin()
 tr.step(batch)
 K.timing_end()
-fan = defaultdict(int)
-for rec in K.FANOUT_LOG:
-    fan[rec] += 1
-print("fan-out backward: (site, autograd grads, sink buf, seeded slice, pending adds, shape) x count")
-for rec, n in sorted(fan.items(), key=lambda kv: str(kv[0])):
-    if rec[1] + int(rec[2]) + rec[4] >= 2:  # something left to sum here
-        print(f"  {n:3d}x {rec}")
 agg = defaultdict(lambda: [0, 0.0, 0])
 for tag, shape, nb, fl, t in K.timing_detail():
     if "ew_kernel" not in tag:

@@ -6,8 +6,8 @@ import os
 import subprocess
 import sys
 
-TOGGLES = ["", "ADR_BN_XF_BWD=0", "ADR_DEFER_DOT=0", "ADR_DEFER_COLSUM=0", "ADR_DEFER_ADD=0", "ADR_FANOUT_SINK=0",
-           "ADR_SEED_CAT=0", "ADR_DCN_FUSED=0", "ADR_GN_FUSED=0", "ADR_DEFER_GN=0", "ADR_EVAL_FUSE=0"]
+TOGGLES = ["", "ADR_FUSE_WG_BIAS=0", "ADR_WG_DB=0", "ADR_DG2H=0", "ADR_DW_RUN=0", "ADR_DW_FUSED=0", "ADR_FIN_PRESUM=0",
+           "ADR_EDFFN_MFMA=0"]
 
 CHILD = r"""
 import sys, json

@@ -32,8 +32,7 @@ def main():
     sys.path.insert(1, str(ROOT))
     from oracle.recipe import synthetic_predictions  # dev script: synthetic head output of the NMS fixtures
     ys = synthetic_predictions(bs, 8400, 80, 640, seed=7).to(dev).contiguous()
-    res = {"shape": list(y.shape), "mode": os.environ.get("ADR_NMS_MODE", "default"),
-           "stop": os.environ.get("ADR_NMS_STOP", "0")}
+    res = {"shape": list(y.shape), "mode": os.environ.get("ADR_NMS_MODE", "default")}
     for name, conf, multi, y in (("predict", 0.25, False, y), ("val", 0.001, True, y),
                                  ("synth_predict", 0.25, False, ys), ("synth_val", 0.001, True, ys)):
         sc = y[:, 4:]

@@ -47,18 +47,8 @@ def timed(f):
     return e0.elapsed_time(e1) / reps * 1e-3
 
 
-import os
 nb_img, nb_y = img.numel(), y.numel() * 2
-outs = {}
-for var in ("0", "1"):  # the previous kernels (env 0) against the current ones
-    os.environ["ADR_STEM_FWD_Q"] = var
-    os.environ["ADR_STEM_WG_Q"] = var
-    for name, f, nb in (("fwd", fwd, nb_img + nb_y), ("wgrad", wgrad, nb_img + nb_y)):
-        t = timed(f)
-        print(f"[{var}] stem {name} N{N} {S}^2 K{Kc}: {t * 1e6:7.1f} us  {nb / t / 1e12:5.2f} TB/s algorithmic "
-              f"({nb / 1e6:.0f} MB)", flush=True)
-    fwd(); wgrad(); torch.cuda.synchronize()
-    outs[var] = (y.float().clone(), stats.clone(), dw.clone())
-for name, a, b in zip(("y", "stats", "dw"), outs["0"], outs["1"]):
-    rel = float((a - b).abs().max() / b.abs().max().clamp_min(1e-30))
-    print(f"{name}: max|new-old|/max|old| = {rel:.3e}  bitwise {torch.equal(a, b)}")
+for name, f, nb in (("fwd", fwd, nb_img + nb_y), ("wgrad", wgrad, nb_img + nb_y)):
+    t = timed(f)
+    print(f"stem {name} N{N} {S}^2 K{Kc}: {t * 1e6:7.1f} us  {nb / t / 1e12:5.2f} TB/s algorithmic "
+          f"({nb / 1e6:.0f} MB)", flush=True)

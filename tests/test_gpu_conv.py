@@ -327,8 +327,7 @@ def test_mul_pixel(dtype, C, hw):
 def test_conv3_wide_tile_bf16(c1, c2, n, hw):
     """The wide 256-pixel x 128-channel 3x3 tile (conv3w_kernel: big-channel convs with >= 512 tiles; l-scale
     shapes) in the forward and the data gradient, with the BN partial statistics, vs torch fp32 on the same bf16
-    operands, and against the 128 x 64 halo-tile kernel it replaces (ADR_CONV3W is read once per process, so the
-    reference here is torch)."""
+    operands (the 128 x 64 halo-tile kernel it replaces serves other shapes only, so the reference here is torch)."""
     from adrefine import kernels as K
     from adrefine.native import lib
     torch.manual_seed(11)

@@ -11,6 +11,7 @@ Every op here launches HIP kernels from libadr_hip.so; nothing falls back to PyT
 from __future__ import annotations
 
 import ctypes
+import os
 import weakref
 
 import torch
@@ -19,18 +20,18 @@ from .native import ConvDesc, lib
 
 F32, BF16 = 0, 1
 ACT = {"none": 0, "silu": 1, "gelu": 2, "relu": 3, "sigmoid": 4, "hswish": 5}
-_NC_MIN_BLOCKS = int(__import__("os").environ.get("ADR_NC_MIN_BLOCKS", 512))
-# 1024 rows per chunk (was 256): fewer partial rows for the finalize kernels to walk; same-box sweep (4 runs each,
-# scripts/ab_sweep.sh r06cb): 256 -> 19.54, 512 -> 19.50, 1024 -> 19.48 ms/step
-_NC_ROWS = int(__import__("os").environ.get("ADR_NC_ROWS", 1024))
+_NC_MIN_BLOCKS = 512
+# 1024 rows per chunk (was 256): fewer partial rows for the finalize kernels to walk; same-box sweep (4 runs each):
+# 256 -> 19.54, 512 -> 19.50, 1024 -> 19.48 ms/step
+_NC_ROWS = 1024
 
 
 def _stats_rows(N, HW):
-    """Rows per adr_nc_reduce chunk: 1024 (ADR_NC_ROWS), shrunk (in multiples of 32) on small maps until the
+    """Rows per adr_nc_reduce chunk: _NC_ROWS, shrunk (in multiples of 32) on small maps until the
     reduction grid has ~_NC_MIN_BLOCKS workgroups — at 20x20 a 256-row chunk leaves 128 workgroups for the
     whole chip."""
     rows = _NC_ROWS
-    if _NC_MIN_BLOCKS and N * -(-HW // rows) < _NC_MIN_BLOCKS:
+    if N * -(-HW // rows) < _NC_MIN_BLOCKS:
         chunks = -(-_NC_MIN_BLOCKS // N)
         rows = max(32, -(-(-(-HW // chunks)) // 32) * 32)
     return rows
@@ -38,7 +39,6 @@ def _stats_rows(N, HW):
 
 # counts layout fix-ups (should stay 0 on the hot path; tests assert it)
 relayout_count = [0]
-_TRACE_RELAYOUT = bool(int(__import__("os").environ.get("ADR_TRACE_RELAYOUT", "0")))
 
 
 # ---------------------------------------------------------------------------------------------------------
@@ -344,9 +344,6 @@ def nhwc(t: torch.Tensor):
     vec = 16 // t.element_size()
     if not ok or t.data_ptr() % 16 or s3 % vec:
         relayout_count[0] += 1
-        if _TRACE_RELAYOUT:
-            import traceback
-            traceback.print_stack(limit=6)
         t = t.contiguous(memory_format=torch.channels_last)
         s3 = t.stride(3)
     return t, t.data_ptr(), s3
@@ -515,7 +512,7 @@ def conv_fwd(d, xp, wp, bias, yp, stats=None, accumulate=0):
 # ADR_CONV_FP8=1); backward stays bf16. Measured (scripts/fp8_micro.py, l-scale 1280^2 bs16 shapes): 3x3 convs
 # with C >= 128 run 1.04-1.24x faster than on the bf16 engine; 1x1 and 64-channel convs are memory-bound and
 # gain nothing (the staging conversion costs VALU), so they stay bf16.
-CONV_FP8 = bool(int(__import__("os").environ.get("ADR_CONV_FP8", "0")))
+CONV_FP8 = bool(int(os.environ.get("ADR_CONV_FP8", "0")))
 _FP8_MIN_C = 128
 
 
@@ -772,13 +769,6 @@ def _nullctx():
     return contextlib.nullcontext()
 
 
-def _dbg_flush(kind, what):
-    if _DEBUG_BNSTAT:
-        import traceback
-        print(f"deferral flush on repeated {kind} destination {what}:", "".join(traceback.format_stack(limit=5)[:-2]),
-              flush=True)
-
-
 class WgradDeferral:
     """Collects the split-K reductions of every conv weight gradient that lands in the trainer's gradient arena
     and runs them as a few batched launches (adr_wgrad_reduce_batched) when the backward pass ends, instead of
@@ -831,7 +821,6 @@ class WgradDeferral:
         """A parameter gradient computed into a temporary, to be added into the arena (sink)."""
         dst = dst.value if isinstance(dst, ctypes.c_void_p) else int(dst)
         if dst in self.adsts:
-            _dbg_flush("axpy", n)
             self.flush()
         self.axpys.append(AxpyEntry(src.data_ptr(), dst, n))
         self.akeep.append(src)
@@ -841,7 +830,6 @@ class WgradDeferral:
         """A bias gradient (adr_partial_sum into the arena), batched the same way."""
         dst = dst.value if isinstance(dst, ctypes.c_void_p) else int(dst)
         if dst in self.pdsts:
-            _dbg_flush("psum", C)
             self.flush()
         self.psums.append(PsumEntry(part.data_ptr(), dst, P, C, which, acc))
         self.pkeep.append(part)
@@ -863,7 +851,6 @@ class WgradDeferral:
     def add(self, ws, stride, splits, dst, K_, C_, Cp, RS_, transpose_kc, acc):
         dst = dst.value if isinstance(dst, ctypes.c_void_p) else int(dst)
         if dst in self.dsts:
-            _dbg_flush("wgrad", (K_, C_, RS_))
             self.flush()
         self.entries.append(WgradEntry(ws.data_ptr(), dst, stride, splits, K_, C_, Cp, RS_, transpose_kc, acc, 0))
         self.keep.append(ws)
@@ -941,15 +928,11 @@ def _defer_dot(param, x, dy):
             _v(x)[1] % 16 == 0)
 
 
-# bias-gradient column sums batched at the flush (ADR_DEFER_COLSUM=0: one adr_nc_reduce per biased conv)
-_DEFER_DOT = bool(int(__import__("os").environ.get("ADR_DEFER_DOT", "1")))  # scalar dot gradients at the flush
-_DEFER_COLSUM = bool(int(__import__("os").environ.get("ADR_DEFER_COLSUM", "1")))
+_DEFER_DOT = True  # 0: scalar dot gradients launched in place; reference of tests/test_gpu_defer.py
+_DEFER_COLSUM = True  # 0: one adr_nc_reduce per biased conv's bias gradient; reference of tests/test_gpu_defer.py
 _DEFER = None  # the active WgradDeferral (set by the trainer around its backward pass)
-# MLCA's two Conv1d weight gradients as partial sums at the flush (ADR_DEFER_MLCA=0: summed at the MLCA backward)
-_DEFER_MLCA = bool(int(__import__("os").environ.get("ADR_DEFER_MLCA", "1")))
-# Partial sets above this size are reduced right away (while still in L2) instead of deferred. Measured
-# (scripts/ab_env.sh): deferring all of them is fastest — 32.39 ms vs 32.49 / 32.64 / 32.70 ms for 16 / 4 / 1 MB.
-DEFER_MAX_BYTES = int(__import__("os").environ.get("ADR_DEFER_MAX_BYTES", 1 << 62))
+# Partial sets of every size are deferred: reducing the large ones right away (while still in L2) measured slower —
+# 32.39 ms/step deferring all vs 32.49 / 32.64 / 32.70 ms with caps of 16 / 4 / 1 MB.
 
 
 def defer_wgrad():
@@ -980,13 +963,13 @@ def _grad_buf(tgt):
 
 
 # WGRAD partials of arena-bound bf16 weight gradients deferred to the stage's flush and grouped into one launch per
-# tile shape (WgradDeferral.add_job; ADR_DEFER_WGRAD=0: one launch per conv, at its backward)
-_DEFER_WGRAD = bool(int(__import__("os").environ.get("ADR_DEFER_WGRAD", "1")))
+# tile shape (WgradDeferral.add_job)
+_DEFER_WGRAD = True  # 0: one launch per conv, at its backward; reference of tests/test_gpu_defer.py
 
 
 def _fuse_wg_bias():
     """ADR_FUSE_WG_BIAS=0: bias gradients by their own column-sum pass (read per call: tests compare the two)."""
-    return __import__("os").environ.get("ADR_FUSE_WG_BIAS", "1") != "0"
+    return os.environ.get("ADR_FUSE_WG_BIAS", "1") != "0"
 
 
 def _bias_rows(bias_param, K, P, part, device):
@@ -1038,8 +1021,7 @@ def _wgrad_param(param, d, xp, dyp, K, C, RS, K_, C_, RS_, cpad, device, keep=()
         return (grad_ret(param, out), bpart is not None,
                 _bias_rows(bias, K, splits, bpart, device) if bpart is not None else None)
 
-    if (_DEFER_WGRAD and keep and _dfr() is not None and acc and d.dtype == BF16 and
-            splits * stride * 4 <= DEFER_MAX_BYTES):
+    if _DEFER_WGRAD and keep and _dfr() is not None and acc and d.dtype == BF16:
         # partials at the flush, grouped with the stage's other convs' (timed there per grouped launch)
         _dfr().add_job(d, xp, dyp, ws, keep, work, shp, bias=bpart)
         _dfr().add(ws, stride, splits, ptr, K_, C_, Cp, RS_, 0, acc)
@@ -1054,7 +1036,7 @@ def _wgrad_param(param, d, xp, dyp, K, C, RS, K_, C_, RS_, cpad, device, keep=()
             lib.adr_conv2d_wgrad_partials(ctypes.byref(d), ctypes.c_void_p(xp), ctypes.c_void_p(dyp), fptr(ws), 0,
                                           stream())
     _t1(tok)
-    if _dfr() is not None and acc and _TIMING is None and splits * stride * 4 <= DEFER_MAX_BYTES:
+    if _dfr() is not None and acc and _TIMING is None:
         _dfr().add(ws, stride, splits, ptr, K_, C_, Cp, RS_, 0, acc)
         return ret()
     tok = _t0("adr::wgrad_reduce_kernel<true, OUT, SL> (split reduce + unpack)",
@@ -1366,9 +1348,6 @@ class BNActFn(torch.autograd.Function):
             part, P = got
         else:
             P = N * chunks
-            if _DEBUG_BNSTAT:
-                print(f"BN bwd stats pass: dz from {getattr(dz, '_adr_src', '?')} {tuple(dz.shape)} act {act} "
-                      f"xfuse {ctx.xfuse} sres {ctx.sres is not None}", flush=True)
             lib.adr_nc_reduce(dt, 1, ctypes.c_void_p(yp), ycs, 0, ctypes.c_void_p(dzp), dzcs, 0, fptr(scale),
                               fptr(shift), 0, ACT[act], N, HW, C, _stats_rows(N, HW), fptr(part), stream())
         lib.adr_bn_bwd_finalize(fptr(part), P, C, float(N * HW), fptr(mean), fptr(rstd),
@@ -1387,12 +1366,12 @@ class BNActFn(torch.autograd.Function):
 # Training Conv-BN-act backward fusion: BNActFn.backward computes the coefficients (nc_reduce + bn_bwd_finalize)
 # but leaves dy = A * dz * act'(y * s + t) + B * y + C unwritten; the producing conv's Conv2dFn.backward runs its
 # data gradient on dz with that transform in the operand staging (adr_conv2d_dgrad_bf16_bnact), which also writes
-# dy once for the weight gradient — the affine_act_bwd pass and its launch disappear. ADR_BN_XF_BWD=0 disables.
-BN_XF_BWD = bool(int(__import__("os").environ.get("ADR_BN_XF_BWD", "1")))
+# dy once for the weight gradient — the affine_act_bwd pass and its launch disappear.
+BN_XF_BWD = True  # 0: affine_act_bwd, then the plain data gradient; reference of tests/test_gpu_bnxf.py
 # The transform is VALU work per staged operand element (a sigmoid for SiLU): measured, the fused data gradient of a
 # 3x3 implicit-GEMM conv (each dz element staged 9x) or of a multi-column-tile 1x1 ran 3x slower than the
 # affine_act_bwd + dgrad pair, so the fusion is taken only where each element is staged about once (x100)
-BN_XF_MAX_REUSE = int(__import__("os").environ.get("ADR_BN_XF_MAX_REUSE", "150"))
+BN_XF_MAX_REUSE = 150
 # data_ptr -> (BnXf, dy): unwritten dy buffers handed to a conv backward. The entry holds dy itself, so its memory
 # cannot be reused by another tensor while the entry exists; entries nobody consumed (a frozen producing conv) are
 # dropped at the end of the backward (defer_wgrad's exit, bnxf_clear)
@@ -1404,11 +1383,10 @@ _BNXF_PENDING = {}
 # (adr_conv2d_fwd_bf16_bnact: streaming 1x1 / 3x3 halo tiles / implicit GEMM) and side-writes z once for the
 # layer's weight gradient — the affine_act pass (a read of y, a launch) disappears. Taken where the consumer stages
 # each element about once (BN_XF_MAX_REUSE); any other reader of a pending z writes it first (nhwc -> _bnf_settle).
-# ADR_BN_XF_FWD=0 disables.
-BN_XF_FWD = bool(int(__import__("os").environ.get("ADR_BN_XF_FWD", "1")))
+BN_XF_FWD = True  # 0: affine_act writes z, then the plain forward conv; reference of tests/test_gpu_bnxf.py
 # the forward transform is one affine + activation per staged element (the backward's needs a second operand and
 # the BN-backward linear term): two column tiles of the streaming 1x1 kernel still qualify
-BN_XF_FWD_MAX_REUSE = int(__import__("os").environ.get("ADR_BN_XF_FWD_MAX_REUSE", "200"))
+BN_XF_FWD_MAX_REUSE = 200
 _BNF_PENDING = {}  # storage data_ptr -> BnFwd
 
 
@@ -1489,17 +1467,14 @@ def bnxf_clear():
 # one reader, the conv that stages it, so that conv's data gradient IS the BN's complete dz. Its epilogue reads y
 # alongside and writes the (sum g, sum g * y) partials adr_nc_reduce's backward pass would (adr_conv2d_dgrad_bf16_bstat),
 # and BNActFn.backward finalizes from them: the nc_reduce launch and its read of dz and y disappear. The sums are
-# the same per-element terms in another order (fixed per geometry: deterministic). ADR_BN_BSTAT=0 disables.
-BN_BSTAT = bool(int(__import__("os").environ.get("ADR_BN_BSTAT", "1")))
+# the same per-element terms in another order (fixed per geometry: deterministic).
+BN_BSTAT = True  # 0: adr_nc_reduce's backward pass over dz and y; reference of tests/test_gpu_bstat.py
 
 
 class BStatStruct(ctypes.Structure):
     """adr_bn_bstat (include/adr.h)."""
     _fields_ = [("y", ctypes.c_void_p), ("scale", ctypes.c_void_p), ("shift", ctypes.c_void_p),
                 ("y_cstride", ctypes.c_int), ("act", ctypes.c_int)]
-
-
-_DEBUG_BNSTAT = bool(int(__import__("os").environ.get("ADR_DEBUG_BNSTAT", "0")))
 
 
 class BnStat:
@@ -1531,9 +1506,6 @@ class BnStat:
         dx = self.ref() if self.ref is not None else None
         ok = (dx is not None and self._key(dz) == self.key and
               (dz is dx or dz.untyped_storage().data_ptr() == dx.untyped_storage().data_ptr()))
-        if _DEBUG_BNSTAT and self.key is not None and not ok:
-            print(f"BnStat.take miss: key {'same' if self._key(dz) == self.key else 'differs'}, dx "
-                  f"{'dead' if dx is None else 'alive'} {tuple(dz.shape)}", flush=True)
         got = (self.part, self.P) if ok else None
         self.part = self.P = self.key = self.ref = None
         return got
@@ -1592,13 +1564,13 @@ class BnXf:
                           self.Cc.data_ptr(), dy.data_ptr(), ycs, dy.stride(3), ACT[self.act], 0)
 
 
-_GN_FUSED = bool(int(__import__("os").environ.get("ADR_GN_FUSED", "1")))  # 0: the 3-launch path (A/B, parity)
+_GN_FUSED = True  # 0: the three-launch path (statistics, finalize, affine + act); reference of tests/test_gpu_gn.py
 # one workgroup per image streams the image twice from one CU: past ~40x40 maps the three-launch path (the whole
 # chip on every pass) is faster
-_GN_FUSED_MAXHW = int(__import__("os").environ.get("ADR_GN_FUSED_MAXHW", "400"))
+_GN_FUSED_MAXHW = 400  # tests/test_gpu_gn.py raises it to take the fused path at every size
 
 
-_DEFER_GN = bool(int(__import__("os").environ.get("ADR_DEFER_GN", "1")))  # 0: GN param grads launched in place
+_DEFER_GN = True  # 0: GroupNorm parameter gradients launched in place; reference of tests/test_gpu_defer.py
 
 
 def _defer_gn(acc):
@@ -1607,7 +1579,6 @@ def _defer_gn(acc):
 
 
 _GATE_GRAD = {}  # dy.data_ptr() -> (weakref to dy, dgate): per-image gate gradients computed by a GN backward
-_GN_GATE = bool(int(__import__("os").environ.get("ADR_GN_GATE", "1")))  # 0: gate gradient from sum(dy * out) (A/B)
 
 
 def _gn_gate_grad(gate, eps, part, ks, N, chunks, sub_rows, C, groups, gammas, mean, rstd, dy):
@@ -1630,7 +1601,7 @@ class GNActFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, y, gamma, beta, groups, act, eps):
         dtype = y.dtype
-        ctx.gate, ctx.eps = getattr(y, "_adr_gate", None) if _GN_GATE else None, eps  # y = s*conv() (ScaleFn)
+        ctx.gate, ctx.eps = getattr(y, "_adr_gate", None), eps  # y = s*conv() (ScaleFn)
         y, yp, ycs = nhwc(y)
         N, C, H, W = y.shape
         HW = H * W
@@ -1802,9 +1773,8 @@ def conv2d(x, w, b=None, stride=1, pad=0, want_stats=False, cpad=0, out=None):
 
 
 # Training conv + bias + activation in one launch for the activations whose derivative follows from the output
-# (relu, sigmoid: the AYHead gates and the cls_prob branch, head.py:135-136, 159-160, 269-270); ADR_CONV_ACT_FUSE=0
-# runs the conv, then the activation kernel
-CONV_ACT_FUSE = bool(int(__import__("os").environ.get("ADR_CONV_ACT_FUSE", "1")))
+# (relu, sigmoid: the AYHead gates and the cls_prob branch, head.py:135-136, 159-160, 269-270)
+CONV_ACT_FUSE = True  # 0: the conv, then the activation kernel; reference of tests/test_gpu_conv.py
 _ONES = {}
 
 
@@ -1898,7 +1868,7 @@ def _bn_eval_coefs(bn, dev):
     return scale, shift
 
 
-EVAL_CONV_BN_ACT = bool(int(__import__("os").environ.get("ADR_EVAL_FUSE", "1")))  # 0: conv, then BN + act
+EVAL_CONV_BN_ACT = True  # 0: conv, then BN + act; reference of tests/test_gpu_conv.py and tests/test_gpu_dwconv.py
 
 
 def conv_bn_act_eval(x, w, stride, pad, bn, act: str, cpad=0, out=None):
@@ -2101,10 +2071,10 @@ class GradSink:
     epilogue (Conv2dFn's dgrad) writes its input gradient here — the first one plainly, later ones accumulating —
     and hands autograd None, so FanOutFn sums one gradient fewer (per conv consumer: a 2-read + 1-write pass and a
     launch become one extra read in the dgrad epilogue). Single stream, so the order is autograd's."""
-    __slots__ = ("buf", "shape", "dtype", "pend", "site")
+    __slots__ = ("buf", "shape", "dtype", "pend")
 
     def __init__(self, shape, dtype):
-        self.buf, self.shape, self.dtype, self.site = None, tuple(shape), dtype, None
+        self.buf, self.shape, self.dtype = None, tuple(shape), dtype
         self.pend = []  # pass-through gradients (AddFn's) waiting to be folded into a conv consumer's dgrad
 
     @staticmethod
@@ -2117,7 +2087,7 @@ class GradSink:
         """Hold a pass-through gradient (a residual add hands its output gradient unchanged to this input): the next
         conv consumer to claim the buffer adds it in its dgrad epilogue, FanOutFn adds whatever is left. bf16 only
         (the bf16 engine's epilogue); `g` is marked so FanOutFn never accumulates into it in place."""
-        if not _DEFER_ADD or g is None or not self.fits(g) or g.dtype != torch.bfloat16 or not self._aligned(g):
+        if g is None or not self.fits(g) or g.dtype != torch.bfloat16 or not self._aligned(g):
             return False
         g._adr_pinned = True
         self.pend.append(g)
@@ -2131,7 +2101,7 @@ class GradSink:
         has claimed one: the convs then accumulate straight into it and FanOutFn gets one gradient fewer to add
         (the acc += sink pass). False when a consumer already claimed a buffer or the slice is not an aligned NHWC
         view the dgrad epilogue can write."""
-        if self.buf is not None or not self.fits(piece) or not _SEED_CAT or not self._aligned(piece):
+        if self.buf is not None or not self.fits(piece) or not self._aligned(piece):
             return False
         self.buf = piece
         return True
@@ -2169,13 +2139,6 @@ def _dx_dst(ctx, shape, dtype, dev):
     return empty_act(*shape, dtype, dev), 0
 
 
-FANOUT_LOG = None  # a list: FanOutFn.backward records (creation site, autograd grads, sink buf, seeded, pending)
-_FANOUT_SINK = bool(int(__import__("os").environ.get("ADR_FANOUT_SINK", "1")))
-_SEED_CAT = bool(int(__import__("os").environ.get("ADR_SEED_CAT", "1")))  # 0: CatFn hands every slice to autograd
-_SHARE_SINK = bool(int(__import__("os").environ.get("ADR_SHARE_SINK", "1")))  # 0: every fan-out owns a sink
-_DEFER_ADD = bool(int(__import__("os").environ.get("ADR_DEFER_ADD", "1")))  # 0: AddFn returns its gradient as is
-
-
 class FanOutFn(torch.autograd.Function):
     """x used by n consumers, as n views. Backward sums the n gradients with HIP launches (one for 2 or 3 of
     them) — into one that is an exclusive concat-gradient slice when there is one (no new buffer, and the split
@@ -2192,12 +2155,7 @@ class FanOutFn(torch.autograd.Function):
     def backward(ctx, *grads):
         gs = [g for g in grads if g is not None]
         sink = ctx.sink
-        if FANOUT_LOG is not None:  # diagnostics (scripts/ew_sites.py): what each fan-out still sums here
-            FANOUT_LOG.append((sink.site if sink is not None else "?", len(gs),
-                               sink is not None and sink.buf is not None,
-                               sink is not None and sink.buf is not None and getattr(sink.buf, "_adr_excl", False),
-                               len(sink.pend) if sink is not None else 0, tuple(gs[0].shape) if gs else None))
-        if sink is not None and sink.buf is not None:  # the consumers that accumulated into the shared buffer
+        if sink.buf is not None:  # the consumers that accumulated into the shared buffer
             # a seeded concat slice (GradSink.seed) goes first: it is the accumulation target below, so x's
             # gradient stays that slice (SplitFn can then join it with its neighbours without a copy)
             if getattr(sink.buf, "_adr_excl", False):
@@ -2205,14 +2163,12 @@ class FanOutFn(torch.autograd.Function):
             else:
                 gs.append(sink.buf)
             sink.buf = None
-        if sink is not None and sink.pend:  # pass-through gradients no conv consumer took
+        if sink.pend:  # pass-through gradients no conv consumer took
             gs.extend(sink.pend)
             sink.pend = []
         if not gs:
             return None, None, None
         if len(gs) == 1:
-            if _DEBUG_BNSTAT:
-                gs[0]._adr_src = "fanout(1)"
             return gs[0], None, None
         dt = gs[0].dtype
         gs = [g if g.dtype == dt else g.to(dt) for g in gs]
@@ -2229,8 +2185,6 @@ class FanOutFn(torch.autograd.Function):
                 else:
                     _ew(EW_COPY, va, _v(rest[0]), accumulate=1)
                     rest = rest[1:]
-            if _DEBUG_BNSTAT:
-                acc._adr_src = f"fanout-excl({len(gs)})"
             return acc, None, None
         out = _new_like(_v(gs[0])[0])
         vo = (out, out.data_ptr(), out.shape[1])
@@ -2247,8 +2201,6 @@ class FanOutFn(torch.autograd.Function):
             else:
                 _ew(EW_COPY, vo, _v(rest[0]), accumulate=1)
                 rest = rest[1:]
-        if _DEBUG_BNSTAT:
-            out._adr_src = f"fanout({len(gs)})"
         return out, None, None
 
 
@@ -2258,19 +2210,10 @@ def fanout(x, n=2):
     # a fan-out of a fan-out view (a block that fans out its input, fed from an outer fan-out) shares the outer
     # sink: consumers on both levels accumulate into one buffer (often the outer's seeded concat slice), so
     # neither FanOutFn has a sum left to launch; each gradient still reaches the outer sum exactly once
-    outer = _sink_of(x) if _SHARE_SINK else None
-    sink = outer if outer is not None else (GradSink(x.shape, x.dtype) if _FANOUT_SINK else None)
-    if sink is not None and outer is None and FANOUT_LOG is not None:
-        import sys
-        f = sys._getframe(1)
-        while f is not None and f.f_code.co_filename == __file__:
-            f = f.f_back
-        if f is not None:
-            sink.site = f"{f.f_code.co_filename.rsplit('/', 1)[-1]}:{f.f_lineno}:{f.f_code.co_name}"
+    sink = _sink_of(x) or GradSink(x.shape, x.dtype)
     outs = FanOutFn.apply(x, n, sink)
-    if sink is not None:
-        for o in outs:
-            o._adr_sink = sink
+    for o in outs:
+        o._adr_sink = sink
     return outs
 
 
@@ -2663,8 +2606,7 @@ class MLCAFn(torch.autograd.Function):
         tl, tg = _target(ctx.pwl), _target(ctx.pwg)
         # both Conv1d weight gradients land in the arena: leave the per-image rows and reduce them at the deferred
         # flush with the other partial sums (no sum launch, no temporaries, no axpy entries)
-        defer = (_DEFER_MLCA and _dfr() is not None and _TIMING is None and tl is not None and tg is not None
-                 and tl is not tg)
+        defer = _dfr() is not None and _TIMING is None and tl is not None and tg is not None and tl is not tg
         dwl = dwg = None
         if not defer:
             dwl = torch.empty(k, dtype=torch.float32, device=y.device)
@@ -2982,31 +2924,18 @@ class PaddedConvFn(torch.autograd.Function):
 def _dcn_fused(dtype, C, Cout, omcs):
     """The bf16 fused DCN kernels (adr_dcn.hip) cover the head's shapes; fp32 parity mode and other shapes take
     im2col + GEMM + the deterministic col2im."""
-    return _DCN_FUSED and dtype == torch.bfloat16 and C % 64 == 0 and Cout % 64 == 0 and Cout <= 256 and \
-        omcs % 8 == 0 and omcs >= 32
-
-
-_DCN_FUSED = bool(int(__import__("os").environ.get("ADR_DCN_FUSED", "1")))  # 0: im2col path (A/B only)
+    return dtype == torch.bfloat16 and C % 64 == 0 and Cout % 64 == 0 and Cout <= 256 and omcs % 8 == 0 and omcs >= 32
 
 
 _DCN_FAR = {}  # device -> (fp32 far-corner buffer, tile flags), grown to the largest shape seen
 _DCN_FAR_RETIRED = []  # outgrown buffers: a captured graph may still address them
 
 
-# 1: a freshly zeroed far-corner pair per backward call (its memset also leaves the buffer in the Infinity Cache
-# right before the kernel's far-corner atomics); 0: one persistent pair per device (the kernels leave it zero)
-_DCN_FAR_FRESH = bool(int(__import__("os").environ.get("ADR_DCN_FAR_FRESH", "0")))
-
-
-def _dcn_far_scratch(dev, N, H, W, C):
-    """Persistent zeroed scratch of adr_dcn_bwd_bf16: the fp32 far-corner buffer and the tile flags. The kernels
-    leave both zero again, so ONE pair per device serves every level, shape, step and graph replay (calls are
-    stream-ordered); a call uses a prefix view of it."""
-    if _DCN_FAR_FRESH:
-        return (torch.zeros(N * H * W * C, dtype=torch.float32, device=dev),
-                torch.zeros(int(lib.adr_dcn_bwd_tiles(N, H, W)), dtype=torch.int32, device=dev))
+def _dcn_far_pair(dev, n, nt):
+    """The device's persistent zeroed (far-corner buffer, tile flags) pair with at least n / nt elements. The
+    kernels leave both zero again, so ONE pair per device serves every level, shape, step and graph replay (calls
+    are stream-ordered). Compared against the FULL pair (not a prefix view), so it grows only when really too small."""
     key = str(dev)
-    n, nt = N * H * W * C, int(lib.adr_dcn_bwd_tiles(N, H, W))
     cur = _DCN_FAR.get(key)
     if cur is None or cur[0].numel() < n or cur[1].numel() < nt:
         if cur is not None:
@@ -3014,28 +2943,23 @@ def _dcn_far_scratch(dev, N, H, W, C):
             n, nt = max(n, cur[0].numel()), max(nt, cur[1].numel())
         cur = (torch.zeros(n, dtype=torch.float32, device=dev), torch.zeros(nt, dtype=torch.int32, device=dev))
         _DCN_FAR[key] = cur
-    return cur[0][:N * H * W * C], cur[1][:int(lib.adr_dcn_bwd_tiles(N, H, W))]
+    return cur
+
+
+def _dcn_far_scratch(dev, N, H, W, C):
+    """Scratch of adr_dcn_bwd_bf16 (the fp32 far-corner buffer and the tile flags): a prefix view of the
+    persistent pair."""
+    n, nt = N * H * W * C, int(lib.adr_dcn_bwd_tiles(N, H, W))
+    f, g = _dcn_far_pair(dev, n, nt)
+    return f[:n], g[:nt]
 
 
 def _dcn_far_scratch_levels(dev, N, dims, C):
     """Per-level disjoint views of the persistent far-corner scratch, for the levels-in-one-launch backward."""
-    n = sum(N * H * W * C for H, W in dims)
-    nt = sum(int(lib.adr_dcn_bwd_tiles(N, H, W)) for H, W in dims)
-    key = str(dev)
-    cur = _DCN_FAR.get(key)
-    if _DCN_FAR_FRESH:
-        cur = (torch.zeros(n, dtype=torch.float32, device=dev), torch.zeros(nt, dtype=torch.int32, device=dev))
-    # compare against the FULL persistent pair (not a prefix view), so it grows only when really too small
-    elif cur is None or cur[0].numel() < n or cur[1].numel() < nt:
-        if cur is not None:
-            _DCN_FAR_RETIRED.append(cur)
-            n, nt = max(n, cur[0].numel()), max(nt, cur[1].numel())
-        _DCN_FAR[key] = cur = (torch.zeros(n, dtype=torch.float32, device=dev),
-                               torch.zeros(nt, dtype=torch.int32, device=dev))
-    f, g = cur
+    sizes = [(N * H * W * C, int(lib.adr_dcn_bwd_tiles(N, H, W))) for H, W in dims]
+    f, g = _dcn_far_pair(dev, sum(k for k, _ in sizes), sum(kt for _, kt in sizes))
     out, o, ot = [], 0, 0
-    for H, W in dims:
-        k, kt = N * H * W * C, int(lib.adr_dcn_bwd_tiles(N, H, W))
+    for k, kt in sizes:
         out.append((f[o:o + k], g[ot:ot + kt]))
         o, ot = o + k, ot + kt
     return out
@@ -3047,8 +2971,8 @@ class DcnLevelStruct(ctypes.Structure):
         (n, ctypes.c_int) for n in ("H", "W", "splits", "pad_")]
 
 
-# the AYHead's DCN levels in one launch per direction (adr_dcn_*_bf16_levels; ADR_DCN_LEVELS=0: one per level)
-DCN_LEVELS = bool(int(__import__("os").environ.get("ADR_DCN_LEVELS", "1")))
+# the AYHead's DCN levels in one launch per direction (adr_dcn_*_bf16_levels)
+DCN_LEVELS = True  # 0: one launch per level; reference of tests/test_gpu_dcn.py
 
 
 def _dcn_work(N, H, W, C, Cout, es=2):
@@ -3244,7 +3168,7 @@ class DWConvFn(torch.autograd.Function):
         ws = torch.empty(wsb // 4 + 1, dtype=torch.float32, device=x.device)
         # weight gradient into the arena: the partial rows now, their reduction batched at the deferred flush
         # (adr_wgrad_reduce_batched with K = 1, RS = k*k: the [C][k*k] parameter layout)
-        defer = pdw is not None and dacc and _dfr() is not None and _TIMING is None and wsb <= DEFER_MAX_BYTES
+        defer = pdw is not None and dacc and _dfr() is not None and _TIMING is None
         if (dx is not None and pdw is not None and
                 lib.adr_dwconv_bwd_fused_supported(dcode(x.dtype), H, W, C, k, vx[2], vd[2], dx.stride(3))):
             # one launch: dx, the weight gradient's partial rows and (where the two-launch path fuses them) the bias rows
@@ -4010,7 +3934,7 @@ class GNPackFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, y, pack, groups, act, eps, per_level, *params):
         dtype = y.dtype
-        ctx.gate, ctx.eps = getattr(y, "_adr_gate", None) if _GN_GATE else None, eps  # y = s*conv() (ScaleFn)
+        ctx.gate, ctx.eps = getattr(y, "_adr_gate", None), eps  # y = s*conv() (ScaleFn)
         y, yp, ycs = nhwc(y)
         Np, C, _, S = y.shape
         dev = y.device
@@ -4188,7 +4112,7 @@ def wgrad_param_multi(param, pieces, K, C, RS, wshape, cpad, device, bias=None):
         s0 += sp
     Cp = max(C_, cpad)
     out, ptr, acc = grad_dst(param, K_ * C_ * RS_, device)
-    if _dfr() is not None and acc and _TIMING is None and s0 * stride * 4 <= DEFER_MAX_BYTES:
+    if _dfr() is not None and acc and _TIMING is None:
         _dfr().add(ws, stride, s0, ptr, K_, C_, Cp, RS_, 0, acc)
     else:
         lib.adr_wgrad_reduce_unpack(fptr(ws), stride, s0, ptr, K_, C_, Cp, RS_, 0, acc, stream())

@@ -1439,24 +1439,6 @@ using namespace adr;
   } while (0)
 
 static constexpr int DW_CB_BF16 = 16, DW_CB_F32 = 8, DW_CB_WG = 8;  // DW_CB_WG: weight-gradient channel slab
-// ADR_DW_IMG=0 routes the forward / data gradient to the direct (global-load) kernel for A/B runs
-static bool dw_img_ok() {
-  static int v = -1;
-  if (v < 0) {
-    const char* e = getenv("ADR_DW_IMG");
-    v = e ? atoi(e) != 0 : 1;
-  }
-  return v != 0;
-}
-// ADR_DW_ROW=0: the per-tap weight-gradient kernel instead of the sliding-window one (A/B)
-static bool dw_row_ok() {
-  static int v = -1;
-  if (v < 0) {
-    const char* e = getenv("ADR_DW_ROW");
-    v = e ? atoi(e) != 0 : 1;
-  }
-  return v != 0;
-}
 constexpr size_t DW_LDS_MAX = 64 * 1024;
 static size_t dw_img_smem_cb(int H, int W, int k, int cb) {  // weight-gradient kernel (fp32 copies in LDS)
   const int p = k / 2;
@@ -1518,7 +1500,7 @@ static size_t dw_run_smem(int H, int W, int k, int images) {
 // The row-run kernel serves the shape class it was measured on: bf16 maps that dw_img_launch runs as F32S (the 20x20
 // C2PTSSA / EDFFN maps), k in {3, 5, 7}. Everything else keeps dw_img_kernel.
 static bool dw_run_shape(int dtype, int H, int W, int C, int k) {
-  return dtype == ADR_BF16 && (k == 3 || k == 5 || k == 7) && C % DW_RUN_CB == 0 && dw_img_ok() &&
+  return dtype == ADR_BF16 && (k == 3 || k == 5 || k == 7) && C % DW_RUN_CB == 0 &&
          dw_f32s(dtype, H, W, k, dw_fwd_cb(dtype, H, W, k));
 }
 template <bool BWD>
@@ -1559,7 +1541,7 @@ extern "C" int adr_dwconv_fwd(int dtype, const void* x, int xcs, const float* w,
   size_t sm = (size_t)k * k * C * sizeof(float);
   ADR_REQUIRE(total < (1l << 32) && sm <= 64 * 1024, "dwconv: N*H*W*C=%ld / k=%d C=%d too large", total, k, C);
   if (dw_run_launch<false>(dtype, st, x, xcs, w, b, y, ycs, N, H, W, C, k, 0)) {
-  } else if (dw_img_ok() && dw_fwd_cb(dtype, H, W, k) && xcs % v == 0 && ycs % v == 0) {
+  } else if (dw_fwd_cb(dtype, H, W, k) && xcs % v == 0 && ycs % v == 0) {
     dw_img_launch<false>(dtype, st, x, xcs, w, b, y, ycs, N, H, W, C, k, 0);
   } else if (dtype == ADR_BF16)
     dw_launch<__bf16, false>(k, dim3(cdiv(total, 256)), sm, st, (const __bf16*)x, xcs, w, b, (__bf16*)y, ycs, N, H, W,
@@ -1571,7 +1553,7 @@ extern "C" int adr_dwconv_fwd(int dtype, const void* x, int xcs, const float* w,
 }
 
 extern "C" int adr_dwconv_fwd_act_supported(int H, int W, int C, int k) {
-  return dw_img_ok() && k % 2 == 1 && C % 8 == 0 && dw_fwd_smem_cb(ADR_BF16, H, W, k, DW_CB_BF16) <= DW_LDS_MAX ? 1 : 0;
+  return k % 2 == 1 && C % 8 == 0 && dw_fwd_smem_cb(ADR_BF16, H, W, k, DW_CB_BF16) <= DW_LDS_MAX ? 1 : 0;
 }
 
 // Eval DWConv-BN-act (reference: Conv.forward_fuse after fuse_conv_and_bn on a depthwise Conv, nn/modules/conv.py:52-54
@@ -1622,7 +1604,7 @@ static int dw_wgrad_partials(int dtype, const void* x, int xcs, const void* dy, 
   const size_t ism = dw_img_smem_cb(H, W, k, wcb);
   const dim3 ig(N, cdiv(C, wcb));
 #define ADR_DWWG(CBV)                                                                                               \
-  if (dtype == ADR_BF16 && dw_row_ok() && (k == 3 || k == 5 || k == 7)) {                                         \
+  if (dtype == ADR_BF16 && (k == 3 || k == 5 || k == 7)) {                                                        \
     if (k == 3)                                                                                                     \
       hipLaunchKernelGGL((dw_wgrad_row_kernel<__bf16, CBV, 3>), ig, dim3(256), ism, st, (const __bf16*)x, xcs,    \
                          (const __bf16*)dy, dcs, H, W, C, ws, bias_part);                                           \
@@ -1658,7 +1640,7 @@ extern "C" int adr_dwconv_bwd(int dtype, const void* x, int xcs, const void* dy,
     size_t sm = (size_t)k * k * C * sizeof(float);
     ADR_REQUIRE(total < (1l << 32) && sm <= 64 * 1024, "dwconv_bwd: N*H*W*C=%ld / k=%d C=%d too large", total, k, C);
     if (dw_run_launch<true>(dtype, st, dy, dcs, w, nullptr, dx, ocs, N, H, W, C, k, accumulate)) {
-    } else if (dw_img_ok() && dw_fwd_cb(dtype, H, W, k) && dcs % v == 0 && ocs % v == 0)
+    } else if (dw_fwd_cb(dtype, H, W, k) && dcs % v == 0 && ocs % v == 0)
       dw_img_launch<true>(dtype, st, dy, dcs, w, nullptr, dx, ocs, N, H, W, C, k, accumulate);
     else if (dtype == ADR_BF16)
       dw_launch<__bf16, true>(k, dim3(cdiv(total, 256)), sm, st, (const __bf16*)dy, dcs, w, nullptr, (__bf16*)dx, ocs, N,
@@ -1705,7 +1687,7 @@ extern "C" int adr_dwconv_wgrad_partials_bias(int dtype, const void* x, int xcs,
 // The one-launch backward serves the row-run shape class when both fp32 images fit the LDS plan and the two-launch
 // path would run the sliding-window weight gradient on 8-channel slabs (the same partial sums, bit for bit).
 extern "C" int adr_dwconv_bwd_fused_supported(int dtype, int H, int W, int C, int k, int xcs, int dcs, int ocs) {
-  return dw_env_on("ADR_DW_FUSED") && dw_run_shape(dtype, H, W, C, k) && dw_row_ok() && xcs % 8 == 0 &&
+  return dw_env_on("ADR_DW_FUSED") && dw_run_shape(dtype, H, W, C, k) && xcs % 8 == 0 &&
                  dcs % 8 == 0 && ocs % 8 == 0 && C / 8 <= 256 && dw_wg_cb(H, W, k) == DW_CB_WG &&
                  dw_run_smem(H, W, k, 2) + 256 * sizeof(float) <= DW_LDS_MAX
              ? 1

@@ -1402,8 +1402,7 @@ static int conv3_tiles(const adr_conv_desc* d, int tw, int pix = 128) {
 // the wide 256-pixel x 128-channel tile (conv3w_kernel, one 512-thread block per CU) for big-channel 3x3 convs with
 // enough tiles to fill the chip twice over
 static bool conv3_wide(const adr_conv_desc* d, int tw, int red_ch, int out_ch) {
-  static const int on = getenv("ADR_CONV3W") ? atoi(getenv("ADR_CONV3W")) : 1;  // A/B
-  return on && tw == 16 && d->h >= 16 && red_ch >= 128 && out_ch % 128 == 0 &&
+  return tw == 16 && d->h >= 16 && red_ch >= 128 && out_ch % 128 == 0 &&
          (long)conv3_tiles(d, 16, 256) * (out_ch / 128) >= 512;
 }
 template <bool DG>
@@ -1535,10 +1534,6 @@ static void launch_conv(int bn, dim3 grid, const ConvArgs& g, hipStream_t st) {
   }
 }
 
-static int conv1_enabled() {
-  static const int on = getenv("ADR_CONV1") ? atoi(getenv("ADR_CONV1")) : 1;  // A/B: 0 = per-tile kernel
-  return on;
-}
 // column-tile count and block groups of a conv1 launch: about one resident wave of blocks (3 or 2 per CU)
 static int conv1_groups(long rows, int ntiles, int kt, int bn) {
   const int mtiles = cdiv(rows, CBM);
@@ -1647,16 +1642,14 @@ static ConvPlan conv_plan(const adr_conv_desc* d, bool dgrad, bool xf = false) {
   {
     // the 128-wide double-buffered tile runs two workgroups per CU; when its grid is under two such rounds of the
     // chip (the n-scale 80^2 -> 40^2 / 40^2 -> 20^2 stride-2 convs: 800 / 200 workgroups), the 64-wide tile's
-    // four per CU fill it better. ADR_CONV_BN_MAX: A/B override (128 = never narrow, 64 = always)
-    const char* e = getenv("ADR_CONV_BN_MAX");
-    const int cap = e ? atoi(e) : 0;
+    // four per CU fill it better
     const long rows = dgrad ? (long)d->n * d->h * d->w : (long)d->n * d->ho * d->wo;
     const long grid128 = (rows + CBM - 1) / CBM * ((out + 127) / 128);
-    if (!p.tw && p.bn == 128 && (cap ? cap < 128 : grid128 < 1024)) p.bn = cap ? (cap >= 16 ? cap : 64) : 64;
+    if (!p.tw && p.bn == 128 && grid128 < 1024) p.bn = 64;
   }
   p.kt = 0;
   const bool c1 = !p.tw && p.mode != CV_DGRAD2 && d->r == 1 && d->s == 1 && d->stride_h == 1 && d->pad_h == 0 &&
-                  d->pad_w == 0 && conv1_enabled();
+                  d->pad_w == 0;
   // forward XF runs on the streaming kernel with the plain forward's tiling (so its output and statistics rows are
   // bitwise the unfused pair's); the data-gradient XF keeps the per-tile kernel
   // KT 256 (1 block per CU) measured a gain for DGRAD only (forward at l-scale 1280^2: 126.5 vs 126.4 ms/step)

@@ -23,8 +23,6 @@
 
 #include "adr_common.h"
 
-#include <cstdlib>
-
 namespace adr {
 
 namespace {
@@ -495,7 +493,7 @@ template <bool LEAN>
 __device__ __forceinline__ int dsw(int row, int e) { return LEAN ? e ^ (((row >> 1) & 3) << 4) : e; }
 
 template <int CC, int CO>
-__device__ __forceinline__ void dcn_bwd_body(const DcnArgs& a, float* dxf, int* flags, int mode, int bid) {
+__device__ __forceinline__ void dcn_bwd_body(const DcnArgs& a, float* dxf, int* flags, int bid) {
   using L = GLds<CC, CO>;
   constexpr bool LEAN = L::LEAN;
   __shared__ __attribute__((aligned(16))) char smem[L::TOTAL];
@@ -534,7 +532,7 @@ __device__ __forceinline__ void dcn_bwd_body(const DcnArgs& a, float* dxf, int* 
   }
 
   // ---------------- phase 1: offset / mask-logit gradients of the tile's 64 output pixels ----------------
-  if (!(mode & 1)) {
+  {  // phase 1's views of reg end here: phase 2 carves it anew
     __bf16* xwin = reinterpret_cast<__bf16*>(reg);
     __bf16* slab0 = reinterpret_cast<__bf16*>(reg + L::P1X);
     __bf16* slab1 = L::SB ? slab0 : slab0 + 64 * L::PW1;
@@ -747,7 +745,6 @@ __device__ __forceinline__ void dcn_bwd_body(const DcnArgs& a, float* dxf, int* 
   }
 
   // ---------------- phase 2: dx of the tile's 64 input pixels ----------------
-  if (mode & 2) return;
   __syncthreads();  // the dom rows are read out of the phase-1 sums that S_t is about to overwrite
   __bf16* dyw = reinterpret_cast<__bf16*>(reg);
   __bf16* S = reinterpret_cast<__bf16*>(reg + L::P2Y);
@@ -876,7 +873,7 @@ __device__ __forceinline__ void dcn_bwd_body(const DcnArgs& a, float* dxf, int* 
       }
       __syncthreads();  // S_t, masks and the W slab complete
       // G_t^T (64 co x this wave's 16 destinations) = dy_sub^T . S_t^T, skipping all-zero K steps
-      const unsigned km = (mode & 4) ? 0xFFFFFFFFu : kmask[4 * (tt & 1) + wave];
+      const unsigned km = kmask[4 * (tt & 1) + wave];
       f32x4 ga[4];
 #pragma unroll
       for (int j = 0; j < 4; ++j) ga[j] = (f32x4){0.f, 0.f, 0.f, 0.f};
@@ -933,13 +930,13 @@ __device__ __forceinline__ void dcn_bwd_body(const DcnArgs& a, float* dxf, int* 
 }
 
 template <int CC, int CO, int OCC>
-__global__ void __launch_bounds__(256, OCC) dcn_bwd_kernel(DcnArgs a, float* dxf, int* flags, int mode) {
-  dcn_bwd_body<CC, CO>(a, dxf, flags, mode, xcd_order(blockIdx.x, gridDim.x));
+__global__ void __launch_bounds__(256, OCC) dcn_bwd_kernel(DcnArgs a, float* dxf, int* flags) {
+  dcn_bwd_body<CC, CO>(a, dxf, flags, xcd_order(blockIdx.x, gridDim.x));
 }
 template <int CC, int CO, int OCC>
-__global__ void __launch_bounds__(256, OCC) dcn_bwd_levels_kernel(DcnLevels L, int mode) {
+__global__ void __launch_bounds__(256, OCC) dcn_bwd_levels_kernel(DcnLevels L) {
   const int b = xcd_order(blockIdx.x, gridDim.x), l = dcn_level(L, b);
-  dcn_bwd_body<CC, CO>(L.a[l], L.dxf[l], L.flags[l], mode, b - L.start[l]);
+  dcn_bwd_body<CC, CO>(L.a[l], L.dxf[l], L.flags[l], b - L.start[l]);
 }
 
 // flagged tiles: dx += dxf (far corners), then dxf and the flag back to zero
@@ -1083,10 +1080,9 @@ extern "C" int adr_dcn_bwd_bf16(const void* x, int xcs, const void* om, int omcs
   a.w_bytes = 9 * C * Cout * 2;
   hipStream_t s = (hipStream_t)stream;
   const int blocks = N * cdiv(H, GT) * cdiv(W, GT);
-  static const int mode = getenv("ADR_DCN_BWD_MODE") ? atoi(getenv("ADR_DCN_BWD_MODE")) : 0;  // A/B: 1/2 skip a phase
-  if (C == 64) hipLaunchKernelGGL((dcn_bwd_kernel<1, 1, 3>), dim3(blocks), dim3(256), 0, s, a, dxf, tile_flags, mode);
-  else if (C == 128) hipLaunchKernelGGL((dcn_bwd_kernel<2, 2, 2>), dim3(blocks), dim3(256), 0, s, a, dxf, tile_flags, mode);
-  else hipLaunchKernelGGL((dcn_bwd_kernel<4, 4, 2>), dim3(blocks), dim3(256), 0, s, a, dxf, tile_flags, mode);
+  if (C == 64) hipLaunchKernelGGL((dcn_bwd_kernel<1, 1, 3>), dim3(blocks), dim3(256), 0, s, a, dxf, tile_flags);
+  else if (C == 128) hipLaunchKernelGGL((dcn_bwd_kernel<2, 2, 2>), dim3(blocks), dim3(256), 0, s, a, dxf, tile_flags);
+  else hipLaunchKernelGGL((dcn_bwd_kernel<4, 4, 2>), dim3(blocks), dim3(256), 0, s, a, dxf, tile_flags);
   if (int rc = check_launch("adr_dcn_bwd_bf16")) return rc;
   hipLaunchKernelGGL(dcn_far_apply_kernel, dim3(blocks), dim3(256), 0, s, a, dxf, tile_flags);
   return check_launch("adr_dcn_bwd_bf16 (far corners)");
@@ -1199,10 +1195,9 @@ extern "C" int adr_dcn_bwd_bf16_levels(const adr_dcn_level* lv, int levels, int 
   }
   L.start[levels] = total;
   hipStream_t s = (hipStream_t)stream;
-  static const int mode = getenv("ADR_DCN_BWD_MODE") ? atoi(getenv("ADR_DCN_BWD_MODE")) : 0;
-  if (C == 64) hipLaunchKernelGGL((dcn_bwd_levels_kernel<1, 1, 3>), dim3(total), dim3(256), 0, s, L, mode);
-  else if (C == 128) hipLaunchKernelGGL((dcn_bwd_levels_kernel<2, 2, 2>), dim3(total), dim3(256), 0, s, L, mode);
-  else hipLaunchKernelGGL((dcn_bwd_levels_kernel<4, 4, 2>), dim3(total), dim3(256), 0, s, L, mode);
+  if (C == 64) hipLaunchKernelGGL((dcn_bwd_levels_kernel<1, 1, 3>), dim3(total), dim3(256), 0, s, L);
+  else if (C == 128) hipLaunchKernelGGL((dcn_bwd_levels_kernel<2, 2, 2>), dim3(total), dim3(256), 0, s, L);
+  else hipLaunchKernelGGL((dcn_bwd_levels_kernel<4, 4, 2>), dim3(total), dim3(256), 0, s, L);
   if (int rc = check_launch("adr_dcn_bwd_bf16_levels")) return rc;
   hipLaunchKernelGGL(dcn_far_apply_levels_kernel, dim3(total), dim3(256), 0, s, L);
   return check_launch("adr_dcn_bwd_bf16_levels (far corners)");

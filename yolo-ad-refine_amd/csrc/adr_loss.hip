@@ -641,16 +641,8 @@ __global__ void __launch_bounds__(256) loss_scalars_kernel(const float* part, in
 //      the softmax expectation), so every access is a 16-byte vector of one row. A block walks 256 anchors;
 //      block partial of sum bce*mod in a fixed-order tree. ----
 // anchors per workgroup of loss_cls_grad_kernel (16 per pass): small, so the whole batch's rows are in flight
-// at once instead of 16 dependent passes per workgroup; ADR_CLS_APB overrides it (multiple of 16) for A/B runs
-static int cls_apb() {
-  static int v = -1;
-  if (v < 0) {
-    const char* e = getenv("ADR_CLS_APB");
-    v = e ? atoi(e) : 32;
-    if (v < 16 || v % 16) v = 32;
-  }
-  return v;
-}
+// at once instead of 16 dependent passes per workgroup (a multiple of 16)
+static constexpr int CLS_APB = 32;
 
 template <typename T>
 __global__ void __launch_bounds__(256) loss_cls_grad_kernel(Levels L, Levels G, int B, int nmax, int nc, float gscale,
@@ -867,7 +859,7 @@ extern "C" int adr_det_loss(int dtype, const void* f0, const void* f1, const voi
   }
   LDISPATCH(loss_fg_kernel, dim3(nblk), dim3(256), L, B, nmax, gt, pbox, align, tgi, fg, pos, tnorm, part);
   hipLaunchKernelGGL(loss_scalars_kernel, dim3(1), dim3(256), 0, st, part, nblk, scal);
-  const int apb = cls_apb();
+  const int apb = CLS_APB;
   LDISPATCH(loss_cls_grad_kernel, dim3(cdiv((long)n, apb)), dim3(256), L, G, B, nmax, nc, grad_scale, gt, pbox, tgi, fg,
             tnorm, scal, part2, box_gain, cls_gain, dfl_gain, apb);
   hipLaunchKernelGGL(loss_final_kernel, dim3(1), dim3(256), 0, st, part2, (int)cdiv((long)n, apb), scal, B, box_gain,

@@ -456,7 +456,6 @@ struct NmsP {
   unsigned long long* best;       // scanned single-label: [B][A] the anchor's key, ~0 if not a candidate
   unsigned long long* masks;      // scanned multi-label: [B][A/64][ng] candidate ballots per 64 anchors and group
   int direct;
-  int stop;                       // ADR_NMS_STOP (phase timing): return after this phase, 0 = run all
 };
 
 __device__ __forceinline__ unsigned long long nms_key(float s, int key) {
@@ -1055,7 +1054,6 @@ __global__ void __launch_bounds__(NMSP_THREADS) nms_persistent_kernel(NmsP p) {
     nmsp_grid_sync(ctl);
     if (blockIdx.x == 0 && tid == 0) st_rlx(&ctl[CTL_REC_OK], 0u);  // every workgroup has read the record
   }
-  if (p.stop == 10) return;
 
   // P0 fill
   if (p.direct) {
@@ -1080,7 +1078,6 @@ __global__ void __launch_bounds__(NMSP_THREADS) nms_persistent_kernel(NmsP p) {
       nmsp_fill_scanned(p, (int)(it / nch64), (int)(it % nch64));
     nmsp_grid_sync(ctl);
   }
-  if (p.stop == 1) return;
 
   // P1 max_nms select (uniform decision: every workgroup reads the same totals)
   bool any_sel = false;
@@ -1162,7 +1159,6 @@ __global__ void __launch_bounds__(NMSP_THREADS) nms_persistent_kernel(NmsP p) {
     }
     nmsp_grid_sync(ctl);
   }
-  if (p.stop == 2) return;
 
   // P2 per (image, group): compact (keys <= threshold), sort, greedy
   for (int item = blockIdx.x; item < B * ng; item += gridDim.x) {
@@ -1195,14 +1191,13 @@ __global__ void __launch_bounds__(NMSP_THREADS) nms_persistent_kernel(NmsP p) {
       while (n < nn) n <<= 1;
       for (int i = nn + tid; i < n; i += NMSP_THREADS) L.sk[i] = ~0ull;
       __syncthreads();
-      if (p.stop != 21) nmsp_bitonic(L.sk, n);
-      if (nn > 0 && p.stop != 20 && p.stop != 21) nk = nmsp_greedy(p, L, b, c, item, nn);
+      nmsp_bitonic(L.sk, n);
+      if (nn > 0) nk = nmsp_greedy(p, L, b, c, item, nn);
     }
     if (tid == 0) a.nkept[item] = nk;
     __syncthreads();
   }
   nmsp_grid_sync(ctl);
-  if (p.stop == 3) return;
 
   // P3 merge per image (workgroup b): the groups' kept lists are gathered into LDS in batches that fit; whenever
   // more than max_det keys are held, an LDS radix select keeps the max_det smallest. The survivors, sorted, are the
@@ -1366,11 +1361,6 @@ int nmsp_grid(int want) {
   return cap < want ? cap : want;
 }
 
-bool getenv_is(const char* k, const char* v) {
-  const char* e = getenv(k);
-  return e && !strcmp(e, v);
-}
-
 bool nms_chain_mode() {
   const char* e = getenv("ADR_NMS_MODE");
   return e && !strcmp(e, "chain");
@@ -1437,13 +1427,11 @@ extern "C" int adr_nms(const float* y, int B, int nc, int A, float conf, float i
   p.tot = p.cur + (size_t)B * a.ng;
   p.ccur = p.tot + B;
   p.hist = p.ccur + B;
-  p.sel_hist = (long)A * (multi ? a.ng : 1) > max_nms && !getenv_is("ADR_NMS_DSEL", "0");
+  p.sel_hist = (long)A * (multi ? a.ng : 1) > max_nms;
   const long waves = (long)B * cdiv(A, 64);
   const long want = std::max<long>(cdiv(waves, NMSP_WAVES), (long)B * a.ng);
   const int grid = nmsp_grid((int)std::min<long>(want, NMSP_MAX_GRID));
   ADR_REQUIRE(grid >= 1, "nms: persistent kernel has no resident capacity");
-  const char* st_env = getenv("ADR_NMS_STOP");
-  p.stop = st_env ? atoi(st_env) : 0;
   hipLaunchKernelGGL(nms_persistent_kernel, dim3(grid), dim3(NMSP_THREADS), 0, st, p);
   return check_launch("adr_nms");
 }

@@ -1206,10 +1206,6 @@ extern "C" int adr_nc_reduce_batched(const adr_colsum_entry* entries, int count,
     }
     ADR_REQUIRE(blocks < (1l << 31), "nc_reduce_batched: grid");
     nb.start[nb.count] = (int)blocks;
-    if (getenv("ADR_DEBUG_NCB"))  // entry table for profiling (one line per entry)
-      for (int j = 0; j < nb.count; ++j)
-        fprintf(stderr, "ncb %d: N=%d HW=%d C=%d xcs=%d rows=%d chunks=%d blocks=%d\n", b0 + j, nb.e[j].N, nb.e[j].HW,
-                nb.e[j].C, nb.e[j].xcs, nb.e[j].rows_per_chunk, nb.e[j].chunks, nb.e[j].N * nb.e[j].chunks);
     hipLaunchKernelGGL(nc_reduce_batched_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, nb);
   }
   return check_launch("adr_nc_reduce_batched");

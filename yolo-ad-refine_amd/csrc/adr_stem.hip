@@ -646,7 +646,7 @@ template <int KT, typename TI>
 __global__ void __launch_bounds__(256) stem_fwd_q_kernel(const TI* __restrict__ img, int H, int W,
                                                          const float* __restrict__ w, __bf16* __restrict__ y, int ycs,
                                                          int Ho, int Wo, float* __restrict__ stats, int nunits, int per,
-                                                         int probe, int N) {
+                                                         int N) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smraw[];
   constexpr int IR = 2 * STEM_ROWS + 1, NR = 3 * IR;
   typedef typename StemQWord<TI>::T Word;
@@ -691,7 +691,7 @@ __global__ void __launch_bounds__(256) stem_fwd_q_kernel(const TI* __restrict__ 
     int n, oy0, ox0;
     unit_geo(u, n, oy0, ox0);
     const int x = 2 * (ox0 + 2 * tid), iy0 = 2 * oy0 - 1;
-    const bool tok = 2 * tid < min(STEM_QSEG, Wo - ox0) && !(probe & 2);
+    const bool tok = 2 * tid < min(STEM_QSEG, Wo - ox0);
     // buffer loads over image n: rows above / below the image, columns past the segment and x - 1 = -1 read
     // out of range, which the hardware returns as zeros (no branch, no select)
     const __amdgpu_buffer_rsrc_t rs =
@@ -747,7 +747,7 @@ __global__ void __launch_bounds__(256) stem_fwd_q_kernel(const TI* __restrict__ 
     const int ybase = (((n * Ho + oy0) * Wo + ox0) * ycs + 4 * g) * 2;  // bytes, < 2^31 (checked by the launcher)
     // fast path (every row a multiple of 64 columns, all pixels valid): blocks of 64 pixels of one row per wave,
     // four 16-pixel steps whose LDS and store addresses differ by immediates, no validity masks
-    const int nb64 = (nox & 63) || (probe & 1) ? 0 : npx / 64;
+    const int nb64 = (nox & 63) ? 0 : npx / 64;
     for (int blk = wave; blk < nb64; blk += 4) {
       const int pb = blk * 64, r = pb / nox, oxb = pb - r * nox;  // scalar
       const uint2* qb = Q + 2 * r * QP + oxb + i;
@@ -792,7 +792,7 @@ __global__ void __launch_bounds__(256) stem_fwd_q_kernel(const TI* __restrict__ 
       uint2 a2 = {0u, 0u};
       if (g == 0) a2 = qb[rC];
       const uint4 b01 = {a0.x, a0.y, a1.x, a1.y}, b2 = {a2.x, a2.y, 0u, 0u};
-      const unsigned yo = pok && !(probe & 1) ? ybase + (r * Wo + ox) * ycs * 2 : 0x7FFFFFF0u;
+      const unsigned yo = pok ? ybase + (r * Wo + ox) * ycs * 2 : 0x7FFFFFF0u;
 #pragma unroll
       for (int t = 0; t < KT; ++t) {
         f32x4 d = {0.f, 0.f, 0.f, 0.f};
@@ -876,10 +876,7 @@ static int stem_fwd(const TI* img, int N, int H, int W, const float* w, int K, v
   ADR_REQUIRE(sm <= 64 * 1024, "stem_conv_fwd: W=%d too wide for the LDS plan", W);
   hipStream_t st = (hipStream_t)stream;
   const dim3 grid(adr_stem_fwd_tiles(N, Ho));
-  const char* qe = getenv("ADR_STEM_FWD_Q");  // A/B, read per call: 0 = the row-gather kernel
-  const char* pe = getenv("ADR_STEM_PROBE");  // diagnostics: 1 = no y stores, 2 = no image loads
-  const int probe = pe ? atoi(pe) : 0;
-  if (W % 4 == 0 && (!qe || atoi(qe))) {
+  if (W % 4 == 0) {  // the quad-image kernel; other widths take the row-gather kernel below
     const size_t qsm = (size_t)3 * (2 * STEM_ROWS + 1) * stem_qp(Wo < STEM_QSEG ? Wo : STEM_QSEG) * 8;
     ADR_REQUIRE(qsm <= 64 * 1024 && 3l * H * W * (long)sizeof(TI) < (1l << 31) && 2l * N * Ho * Wo * ycs < (1l << 31),
                 "stem_conv_fwd: quad image %zu bytes / 32-bit buffer offsets", qsm);
@@ -894,11 +891,11 @@ static int stem_fwd(const TI* img, int N, int H, int W, const float* w, int K, v
     const int per = ((int)grid.x + cus * occ - 1) / (cus * occ) * segs;
     const dim3 qgrid((nunits + per - 1) / per);
     if (K == 16)
-      hipLaunchKernelGGL((stem_fwd_q_kernel<1, TI>), qgrid, dim3(256), qsm, st, img, H, W, w, (__bf16*)y, ycs, Ho, Wo, stats, nunits, per, probe, N);
+      hipLaunchKernelGGL((stem_fwd_q_kernel<1, TI>), qgrid, dim3(256), qsm, st, img, H, W, w, (__bf16*)y, ycs, Ho, Wo, stats, nunits, per, N);
     else if (K == 32)
-      hipLaunchKernelGGL((stem_fwd_q_kernel<2, TI>), qgrid, dim3(256), qsm, st, img, H, W, w, (__bf16*)y, ycs, Ho, Wo, stats, nunits, per, probe, N);
+      hipLaunchKernelGGL((stem_fwd_q_kernel<2, TI>), qgrid, dim3(256), qsm, st, img, H, W, w, (__bf16*)y, ycs, Ho, Wo, stats, nunits, per, N);
     else
-      hipLaunchKernelGGL((stem_fwd_q_kernel<4, TI>), qgrid, dim3(256), qsm, st, img, H, W, w, (__bf16*)y, ycs, Ho, Wo, stats, nunits, per, probe, N);
+      hipLaunchKernelGGL((stem_fwd_q_kernel<4, TI>), qgrid, dim3(256), qsm, st, img, H, W, w, (__bf16*)y, ycs, Ho, Wo, stats, nunits, per, N);
     return check_launch("adr_stem_conv_fwd");
   }
   if (K == 16)
@@ -943,14 +940,13 @@ static int stem_wgrad(const TI* img, int N, int H, int W, const void* dy, int dc
   ADR_REQUIRE(sm <= 64 * 1024 && dcs % 8 == 0, "stem_conv_wgrad: W=%d too wide for the LDS plan", W);
   hipStream_t st = (hipStream_t)stream;
   int nblk = blocks;
-  const char* qe = getenv("ADR_STEM_WG_Q");  // A/B, read per call: 0 = the row-gather kernels
   const int qseg = Wo < stem_wq_seg(KT) ? Wo : stem_wq_seg(KT);
   const size_t qsm_rows = (((size_t)3 * 3 * (2 * STEM_ROWS + 1) * (qseg + STEM_PP_PAD) + 7) & ~(size_t)7) * 2 +
                           (size_t)STEM_ROWS * qseg * KT * 16 * 2;
   const size_t qsm_red = (size_t)4 * KT * 16 * 32 * 4;
   const size_t qsm = qsm_rows > qsm_red ? qsm_rows : qsm_red;
   // whole 32-pixel steps per tile, 4-pixel runs within a row, 16-byte image words per thread pair
-  if (W % 4 == 0 && Wo % qseg == 0 && qseg % 16 == 0 && qsm <= 64 * 1024 && (!qe || atoi(qe))) {
+  if (W % 4 == 0 && Wo % qseg == 0 && qseg % 16 == 0 && qsm <= 64 * 1024) {
     const int qtiles = N * ((Ho + STEM_ROWS - 1) / STEM_ROWS) * (Wo / qseg);
     auto kern = K == 16 ? (const void*)stem_wgrad_q_kernel<1, TI>
                         : K == 32 ? (const void*)stem_wgrad_q_kernel<2, TI> : (const void*)stem_wgrad_q_kernel<4, TI>;

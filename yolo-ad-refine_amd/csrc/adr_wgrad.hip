@@ -633,16 +633,6 @@ static int wg3_tw(const adr_conv_desc* d) {
   return 0;
 }
 
-// ADR_WGRAD_THIN=0 routes the thin-channel shapes back to the general kernel (A/B runs)
-static bool thin_enabled() {
-  static int v = -1;
-  if (v < 0) {
-    const char* e = getenv("ADR_WGRAD_THIN");
-    v = e ? atoi(e) != 0 : 1;
-  }
-  return v != 0;
-}
-
 // the 128 x 128 tile runs double-buffered (wgrad_bf16_body<.., DB = true>, bitwise the single-stage loop);
 // ADR_WG_DB=0 selects the single-stage kernel (A/B; read per launch, so a test can switch it in-process)
 static bool wg_db() {
@@ -667,18 +657,17 @@ static void launch_bm(int bn, dim3 grid, const WgArgs& g, hipStream_t st) {
   }
 }
 
-// tiles, k-step rows and split count for a bf16 WGRAD; splits bounded so the fp32 partials stay small
-// (ADR_WG_PART_MB / ADR_WG3_PART_MB override the per-conv partial budgets of the generic / 3x3-halo plans, A/B only)
-static long part_budget(const char* var, long def_mb) {
-  const char* e = getenv(var);
-  const long v = e ? atol(e) : def_mb;
-  return (v > 0 ? v : def_mb) << 20;
-}
+// tiles, k-step rows and split count for a bf16 WGRAD; splits bounded so the fp32 partials stay small: the per-conv
+// partial budgets of the 3x3-halo plan, and of the generic plan for weights up to / above 1 MB
+static constexpr long WG3_PART_BYTES = 64l << 20;
+static constexpr long WG_PART_BYTES = 24l << 20;
+static constexpr long WG_PART_BYTES_BIG = 96l << 20;
+static constexpr long WG_MIN_KSTEPS = 16;  // k-steps per split at least (8 before the launches were grouped)
 
 WgPlan wgrad_bf16_plan(const adr_conv_desc* d) {
   WgPlan p;
   p.tw3 = 0;
-  p.thin = thin_enabled() ? wg3_thin(d) : 0;
+  p.thin = wg3_thin(d);
   if (p.thin) {
     const long ntile = (long)d->n * ((d->ho + 7) / 8) * (d->wo / 16);
     p.bm = d->k <= 16 ? 16 : 32;
@@ -704,8 +693,7 @@ WgPlan wgrad_bf16_plan(const adr_conv_desc* d) {
     p.tiles = (d->k / p.bm) * (d->c / 32);
     long s = (768 + p.tiles - 1) / p.tiles;                      // ~3 workgroups per CU
     const long by_work = ntile / 4;                              // >= 4 tiles per split
-    static const long b3 = part_budget("ADR_WG3_PART_MB", 64);
-    const long by_bytes = b3 / ((long)d->k * 9 * d->c * 4);
+    const long by_bytes = WG3_PART_BYTES / ((long)d->k * 9 * d->c * 4);
     if (s > by_work) s = by_work;
     if (s > by_bytes) s = by_bytes;
     if (s < 1) s = 1;
@@ -722,13 +710,10 @@ WgPlan wgrad_bf16_plan(const adr_conv_desc* d) {
   const long outsz = (long)d->k * d->r * d->s * d->c;
   p.tiles = cdiv(d->k, p.bm) * d->r * d->s * cdiv(d->c, p.bn);
   long s = (1024 + p.tiles - 1) / p.tiles;                  // ~4 workgroups per CU
-  static const long min_ks = getenv("ADR_WG_MIN_KSTEPS") ? atol(getenv("ADR_WG_MIN_KSTEPS")) : 16;  // A/B (8 before grouping)
-  const long by_work = red / ((long)p.R * min_ks);          // >= 16 k-steps per split (grouped launches fill the chip)
+  const long by_work = red / ((long)p.R * WG_MIN_KSTEPS);   // grouped launches fill the chip
   // <= 24 MB of partials (stays in L2/MALL); weights above 1 MB (l-scale: 3x3 256->256, 1x1 512->512) get 96 MB so
   // their splits still fill the chip (configs[4]: 145.2 -> 142.2 ms/step; the n-scale step is unchanged)
-  static const long bg = part_budget("ADR_WG_PART_MB", 24);
-  static const bool bg_env = getenv("ADR_WG_PART_MB") != nullptr;
-  const long by_bytes = (!bg_env && outsz * 4 > (1l << 20) ? (96l << 20) : bg) / (outsz * 4);
+  const long by_bytes = (outsz * 4 > (1l << 20) ? WG_PART_BYTES_BIG : WG_PART_BYTES) / (outsz * 4);
   if (s > by_work) s = by_work;
   if (s > by_bytes) s = by_bytes;
   if (s < 1) s = 1;
