@@ -1,7 +1,9 @@
 """Post-processing on the device — drop-in for the reference's ultralytics/utils/ops.py:163-312
 `non_max_suppression` (the detect predict/val callers: models/yolo/detect/predict.py:25,
 models/yolo/detect/val.py:94). The whole batch runs in one persistent HIP launch (adr_nms: candidate
-extraction, max_nms radix select, per-class greedy NMS, max_det merge, separated by grid barriers); the only host sync is reading the per-image counts to
+extraction, max_nms radix select, per-class greedy NMS, max_det merge, separated by grid barriers); above 16 384
+predictions per image (inputs over 864 x 864) the same stages run as six plain launches whose per-class sort spills
+from LDS to global memory. The only host sync is reading the per-image counts to
 split the padded result into the reference's list of (n, 6) tensors."""
 from __future__ import annotations
 
@@ -13,13 +15,18 @@ from ..kernels import fptr, stream
 from ..native import lib
 
 _WS = {}
+_WS_SUPERSEDED = {}  # device -> the smaller workspaces _WS[device] replaced
 
 
 def _workspace(device, nbytes):
     """adr_nms keeps its grid barrier's control words in the first 64 bytes of the workspace: zero on first use
-    (the buffer is zero-filled when (re)allocated) and left zero by every call."""
+    (the buffer is zero-filled when (re)allocated) and left zero by every call. A workspace that a larger one
+    replaces stays referenced: a FusedPredictor hipGraph captured earlier still writes into it (the hazard
+    check_counts describes), and a 1280^2 call after a 640^2 graph makes that the normal case."""
     ws = _WS.get(device)
     if ws is None or ws.numel() < nbytes:
+        if ws is not None:
+            _WS_SUPERSEDED.setdefault(device, []).append(ws)
         ws = torch.zeros(nbytes, dtype=torch.uint8, device=device)
         _WS[device] = ws
     return ws

@@ -8,6 +8,8 @@
 // (image, class) sorts its bucket (bitonic, LDS) and runs the greedy scan with wave ballots; a final merge
 // takes the best max_det survivors per image in (score desc, candidate order asc) order.
 // Compiled with -ffp-contract=off (Makefile) so no FMA changes IoU rounding.
+// Three pipelines share the stages: A <= 16384 runs the persistent single launch (default) or this six-kernel chain
+// (ADR_NMS_MODE=chain); A > 16384 runs the chain with a class stage whose sort spills to global memory.
 #include "adr_common.h"
 
 #include <algorithm>
@@ -16,7 +18,9 @@
 
 namespace adr {
 
-static constexpr int NMS_SORT_CAP = 16384;  // per-(image, class) bucket capacity (A <= 16384, i.e. <= 896^2 input)
+// keys one LDS sort holds (128 KiB of u64). A <= NMS_SORT_CAP (square inputs up to 864^2; 896^2 has 16 464
+// predictions) bounds every bucket by it; a larger A takes the class stage that spills (nms_class_large_kernel)
+static constexpr int NMS_SORT_CAP = 16384;
 
 struct NmsArgs {
   const float* y;   // (B, 4+nc, A)
@@ -394,6 +398,229 @@ __global__ void __launch_bounds__(64) nms_merge_kernel(NmsArgs a) {
     __syncthreads();
   }
   if (lane == 0) a.nout[b] = nout;
+}
+
+// ---------------- class stage for A > NMS_SORT_CAP ----------------
+// The chain above with this kernel in place of nms_class_kernel is the whole path for A > NMS_SORT_CAP: plain
+// back-to-back launches, no grid barrier, no wait on another workgroup. One 1024-thread workgroup per (image, group):
+//   compact  the bucket's candidates that survive the max_nms threshold become 64-bit keys (~score_bits << 32 | order
+//            key: unique per image, the reference's order), in LDS when the bucket's pre-select count fits, else in the
+//            bucket's slice of a global u64 array; each survivor's slot is recorded under its order key (the merge
+//            stage reads scores and classes by slot);
+//   sort     <= NMS_SORT_CAP survivors: a bitonic network in LDS. More: the same network over the global array, in
+//            which every step whose partners lie within one aligned NMS_SORT_CAP-key tile runs on the tile staged in
+//            LDS and only the steps that cross tiles are compare-exchanges in global memory (one for 32 768 keys,
+//            three for 65 536), separated by workgroup barriers and workgroup-scope fences;
+//   greedy   one wave over the sorted keys, 64 at a time, the arithmetic of nms_class_kernel.
+// The network is the merge-sort form whose compare-exchanges all point upwards: sorted runs of k/2 keys are merged by
+// one "flip" step (i against the mirrored position of the other run) and half-cleaners of stride k/4 .. 1. Keys past
+// the end count as +inf and a pair with such a partner is skipped, so any length sorts without padding the array.
+static constexpr int NMSL_THREADS = 1024;
+
+struct NmsLarge {
+  NmsArgs a;
+  unsigned long long* gk;  // [B][cap] sort keys of the buckets that spill (bucket at offs, as the candidate arrays)
+  int* slot;               // [B][cap] order key -> candidate slot within the image
+};
+
+struct NmslLds {
+  unsigned long long sk[NMS_SORT_CAP];  // 128 KiB: one workgroup per CU
+  float kb[300][4];
+  float ka[300];
+  int cnt;
+};
+
+__device__ __forceinline__ void nmsl_sync() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+  __syncthreads();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+}
+
+__device__ __forceinline__ void nmsl_cmpx(unsigned long long* v, long i, long j) {
+  const unsigned long long x = v[i], y = v[j];
+  if (x > y) {
+    v[i] = y;
+    v[j] = x;
+  }
+}
+
+// flip step of run length k over v[0..n): pair t is (s + r, s + k - 1 - r), s = (t / (k/2)) * k, r = t % (k/2)
+__device__ __forceinline__ void nmsl_flip(unsigned long long* v, long n, long k) {
+  const long h = k >> 1;
+  for (long t = threadIdx.x;; t += NMSL_THREADS) {
+    const long r = t & (h - 1), s = (t / h) * k, i = s + r, j = s + k - 1 - r;
+    if (i >= n) break;  // i grows with t
+    if (j < n) nmsl_cmpx(v, i, j);
+  }
+}
+
+// half-cleaner of one stride over v[0..n)
+__device__ __forceinline__ void nmsl_clean(unsigned long long* v, long n, long stride) {
+  for (long t = threadIdx.x;; t += NMSL_THREADS) {
+    const long i = (t / stride) * 2 * stride + (t & (stride - 1)), j = i + stride;
+    if (i >= n) break;
+    if (j < n) nmsl_cmpx(v, i, j);
+  }
+}
+
+// LDS: half-cleaners of stride0, stride0 / 2, .. 1, then the whole sort of sk[0..n)
+__device__ void nmsl_lds_cleans(unsigned long long* sk, int n, int stride0) {
+  for (int stride = stride0; stride > 0; stride >>= 1) {
+    nmsl_clean(sk, n, stride);
+    __syncthreads();
+  }
+}
+
+__device__ void nmsl_lds_sort(unsigned long long* sk, int n) {
+  for (int k = 2; (k >> 1) < n; k <<= 1) {
+    nmsl_flip(sk, n, k);
+    __syncthreads();
+    nmsl_lds_cleans(sk, n, k >> 2);
+  }
+}
+
+// every NMS_SORT_CAP-key tile of g[0..n) through LDS: sorted (stride0 < 0) or half-cleaned from stride0 down
+__device__ void nmsl_tiles(unsigned long long* g, long n, NmslLds& L, int stride0) {
+  for (long base = 0; base < n; base += NMS_SORT_CAP) {
+    const int m = (int)(n - base < NMS_SORT_CAP ? n - base : NMS_SORT_CAP);
+    for (int i = threadIdx.x; i < m; i += NMSL_THREADS) L.sk[i] = g[base + i];
+    __syncthreads();
+    if (stride0 < 0)
+      nmsl_lds_sort(L.sk, m);
+    else
+      nmsl_lds_cleans(L.sk, m, stride0);
+    for (int i = threadIdx.x; i < m; i += NMSL_THREADS) g[base + i] = L.sk[i];
+    nmsl_sync();
+  }
+}
+
+__device__ void nmsl_global_sort(unsigned long long* g, long n, NmslLds& L) {
+  nmsl_tiles(g, n, L, -1);
+  for (long k = 2l * NMS_SORT_CAP; (k >> 1) < n; k <<= 1) {
+    nmsl_flip(g, n, k);
+    nmsl_sync();
+    for (long stride = k >> 2; stride >= NMS_SORT_CAP; stride >>= 1) {
+      nmsl_clean(g, n, stride);
+      nmsl_sync();
+    }
+    nmsl_tiles(g, n, L, NMS_SORT_CAP >> 1);
+  }
+}
+
+// greedy scan by wave 0 over the sorted keys[0..n) (LDS or global), as nms_class_kernel's
+__device__ void nmsl_greedy(const NmsLarge& p, NmslLds& L, const unsigned long long* keys, int n, int b, int c) {
+  const NmsArgs& a = p.a;
+  const int lane = threadIdx.x;
+  const float offc = a.agnostic ? 0.f : (float)c * a.max_wh;  // x[:, 5:6] * (0 if agnostic else max_wh)
+  const int* slot = p.slot + (long)b * a.cap;
+  int nk = 0;
+  bool done = false;
+  for (int t0 = 0; t0 < n && !done; t0 += 64) {
+    const unsigned long long v = t0 + lane < n ? keys[t0 + lane] : ~0ull;
+    const int key = (int)(unsigned)v;
+    float q0 = 0.f, q1 = 0.f, q2 = 0.f, q3 = 0.f;
+    if (v != ~0ull) {
+      float bx[4];
+      box_of(a, b, key, bx);
+      q0 = bx[0] + offc;
+      q1 = bx[1] + offc;
+      q2 = bx[2] + offc;
+      q3 = bx[3] + offc;
+    }
+    const unsigned long long live = __ballot(v != ~0ull);
+    for (int j = 0; j < 64; ++j) {
+      if (!((live >> j) & 1ull) || nk >= a.max_det) {
+        done = true;
+        break;
+      }
+      const float o0 = __shfl(q0, j, 64), o1 = __shfl(q1, j, 64), o2 = __shfl(q2, j, 64), o3 = __shfl(q3, j, 64);
+      const int cand = __shfl(key, j, 64);
+      const float area = (o2 - o0) * (o3 - o1);
+      bool sup = false;
+      for (int k0 = 0; k0 < nk && !sup; k0 += 64) {
+        const int k = k0 + lane;
+        bool s = false;
+        if (k < nk) {
+          const float xx1 = fmaxf(L.kb[k][0], o0), yy1 = fmaxf(L.kb[k][1], o1);
+          const float xx2 = fminf(L.kb[k][2], o2), yy2 = fminf(L.kb[k][3], o3);
+          const float w = fmaxf(0.f, xx2 - xx1), h = fmaxf(0.f, yy2 - yy1);
+          const float inter = w * h;
+          const float ovr = inter / (L.ka[k] + area - inter);  // torchvision: inter / (iarea + areas[j] - inter)
+          s = ovr > a.iou;
+        }
+        sup = __ballot(s) != 0ull;
+      }
+      if (!sup) {
+        if (lane == 0) {
+          L.kb[nk][0] = o0;
+          L.kb[nk][1] = o1;
+          L.kb[nk][2] = o2;
+          L.kb[nk][3] = o3;
+          L.ka[nk] = area;
+          a.kept[((long)b * a.ng + c) * a.max_det + nk] = slot[cand];
+        }
+        __builtin_amdgcn_wave_barrier();
+        nk++;
+      }
+    }
+  }
+  if (lane == 0) a.nkept[b * a.ng + c] = nk;
+}
+
+__global__ void __launch_bounds__(NMSL_THREADS) nms_class_large_kernel(NmsLarge p) {
+  const NmsArgs& a = p.a;
+  const int b = blockIdx.x / a.ng, c = blockIdx.x % a.ng;  // c: group (class, or 0 when agnostic)
+  const int n0 = a.counts[b * a.ng + c], off = a.offs[b * a.ng + c];
+  const int tid = threadIdx.x, lane = tid & 63;
+  if (n0 == 0) {
+    if (tid == 0) a.nkept[b * a.ng + c] = 0;
+    return;
+  }
+  __shared__ NmslLds L;
+  const float* sc = a.cscore + (long)b * a.cap + off;
+  const int* ky = a.ckey + (long)b * a.cap + off;
+  int* slot = p.slot + (long)b * a.cap;
+  unsigned long long* g = p.gk + (long)b * a.cap + off;  // n0 slots: the survivors fit
+  const unsigned tb = a.thr[b * 2], tk = a.thr[b * 2 + 1];
+  const bool spill = n0 > NMS_SORT_CAP;  // block-uniform
+  unsigned long long* dst = spill ? g : L.sk;
+  if (tid == 0) L.cnt = 0;
+  __syncthreads();
+  for (int i0 = (tid >> 6) * 64; i0 < n0; i0 += NMSL_THREADS) {
+    const int i = i0 + lane;
+    bool keep = false;
+    unsigned long long v = ~0ull;
+    if (i < n0) {
+      const unsigned bits = __float_as_uint(sc[i]);
+      const int key = ky[i];
+      keep = keep_after_select(bits, (unsigned)key, tb, tk);
+      if (keep) {
+        v = ((unsigned long long)(~bits) << 32) | (unsigned)key;
+        slot[key] = off + i;
+      }
+    }
+    const unsigned long long m = __ballot(keep);
+    if (!m) continue;
+    int base = 0;
+    if (lane == 0) base = atomicAdd(&L.cnt, __popcll(m));
+    base = __shfl(base, 0, 64);
+    if (keep) dst[base + __popcll(m & ((1ull << lane) - 1ull))] = v;
+  }
+  nmsl_sync();
+  const int nn = L.cnt;  // <= n0
+  const unsigned long long* sorted = L.sk;
+  if (nn > NMS_SORT_CAP) {
+    nmsl_global_sort(g, nn, L);
+    sorted = g;
+  } else {
+    if (spill) {
+      for (int i = tid; i < nn; i += NMSL_THREADS) L.sk[i] = g[i];
+      __syncthreads();
+    }
+    nmsl_lds_sort(L.sk, nn);
+  }
+  if (tid >= 64) return;
+  nmsl_greedy(p, L, sorted, nn, b, c);
 }
 
 // ---------------- persistent single-launch variant (the default) ----------------
@@ -1311,6 +1538,14 @@ void carve_chain(NmsArgs& a, WsCarve& w, int B, int nc, int A, int multi, int ma
   a.ccnt = w.take<int>((size_t)B * cdiv(A, 256) * nc);
 }
 
+// A > NMS_SORT_CAP: the chain layout, then the spill keys and the slot map
+void carve_large(NmsLarge& l, WsCarve& w, int B, int nc, int A, int multi, int max_det) {
+  const size_t cap = (size_t)A * (multi ? nc : 1);
+  carve_chain(l.a, w, B, nc, A, multi, max_det);
+  l.gk = w.take<unsigned long long>(B * cap);
+  l.slot = w.take<int>(B * cap);
+}
+
 void carve_persistent(NmsP& p, WsCarve& w, int B, int nc, int A, int multi, int max_det, bool direct) {
   const size_t cap = (size_t)A * (multi ? nc : 1);
   // fill cursors, per-image totals, select compaction cursors, top-digit histograms (contiguous: one record)
@@ -1373,6 +1608,11 @@ extern "C" size_t adr_nms_workspace(int B, int nc, int A, int multi, int max_det
   WsCarve z{nullptr};
   carve_zero(p, z);
   WsCarve c{nullptr, z.used}, q{nullptr, z.used};
+  if (A > NMS_SORT_CAP) {
+    NmsLarge l{};
+    carve_large(l, c, B, nc, A, multi, max_det);
+    return c.used + 256;
+  }
   carve_chain(p.a, c, B, nc, A, multi, max_det);
   carve_persistent(p, q, B, nc, A, multi, max_det, nms_direct(B, nc, A));
   return (c.used > q.used ? c.used : q.used) + 256;
@@ -1394,9 +1634,11 @@ extern "C" int adr_nms_reset(void* ws, size_t ws_bytes, void* stream) {
 extern "C" int adr_nms(const float* y, int B, int nc, int A, float conf, float iou, int multi, int agnostic,
                        const unsigned char* class_mask, int max_det, int max_nms, float max_wh, float* out, int* nout,
                        void* ws, size_t ws_bytes, void* stream) {
-  ADR_REQUIRE(B > 0 && nc >= 1 && nc <= 1024 && max_det >= 1 && max_det <= 300 && A >= 1 && A <= NMS_SORT_CAP &&
-                  max_nms >= 1,
+  ADR_REQUIRE(B > 0 && nc >= 1 && nc <= 1024 && max_det >= 1 && max_det <= 300 && A >= 1 && max_nms >= 1,
               "nms: B=%d nc=%d max_det=%d A=%d max_nms=%d unsupported", B, nc, max_det, A, max_nms);
+  ADR_REQUIRE((long)A * nc < (1l << 31),
+              "nms: A=%d nc=%d: the candidate order key anchor * nc + class is an int, so A * nc must stay below 2^31",
+              A, nc);
   ADR_REQUIRE(!(agnostic && multi), "nms: agnostic multi-label groups exceed the per-group sort capacity");
   ADR_REQUIRE(ws_bytes >= adr_nms_workspace(B, nc, A, multi, max_det), "nms: workspace");
   NmsP p{};
@@ -1410,6 +1652,20 @@ extern "C" int adr_nms(const float* y, int B, int nc, int A, float conf, float i
   WsCarve w{(char*)ws};
   carve_zero(p, w);
   hipStream_t st = (hipStream_t)stream;
+  if (A > NMS_SORT_CAP) {  // count, scan, fill, select as the chain; the class stage that spills; merge
+    NmsLarge l{};
+    l.a = a;
+    l.a.rec_ok = p.ctl + CTL_REC_OK;
+    carve_large(l, w, B, nc, A, multi, max_det);
+    const int nch = cdiv(A, 256);
+    hipLaunchKernelGGL(nms_count_kernel, dim3(nch, B), dim3(256), 0, st, l.a);
+    hipLaunchKernelGGL(nms_scan_kernel, dim3(B), dim3(256), 0, st, l.a, nch);
+    hipLaunchKernelGGL(nms_fill_kernel, dim3(nch, B), dim3(256), 0, st, l.a);
+    hipLaunchKernelGGL(nms_select_kernel, dim3(B), dim3(256), 0, st, l.a);
+    hipLaunchKernelGGL(nms_class_large_kernel, dim3(B * a.ng), dim3(NMSL_THREADS), 0, st, l);
+    hipLaunchKernelGGL(nms_merge_kernel, dim3(B), dim3(64), 0, st, l.a);
+    return check_launch("adr_nms");
+  }
   if (nms_chain_mode()) {
     a.rec_ok = p.ctl + CTL_REC_OK;
     carve_chain(a, w, B, nc, A, multi, max_det);
