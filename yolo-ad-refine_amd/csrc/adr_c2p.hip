@@ -740,7 +740,9 @@ __global__ void adyt_alpha_kernel(const float* dan, const float* imp, int N, flo
 // (scripts/tssa_ab.py), but with them the fp32 gradient arena of the packed-head trainer test
 // (test_gpu_packed_head.py) drifted 200x further from the per-level loop (2.4e-4 vs 1.2e-6 relative, uniformly
 // over the backbone and neck, scripts/packed_arena_diff.py); at 512 it is 1.1e-6. Not explained; the launches run
-// 512 threads.
+// 512 threads. Against the float64 op-level reference (tests/test_gpu_token_ops.py, N = 400, B = 2, temperatures 1
+// and 30) the 512-thread fp32 kernels are at max|err| / max|ref| = 6.4e-6 (out), 5.1e-6 (dk, dv), and the analytically
+// zero dq and dtemp stay below 1.2e-2 of their bounds: the committed variant is right to fp32 rounding.
 #ifndef TSSA_NTH
 #define TSSA_NTH 512
 #endif
