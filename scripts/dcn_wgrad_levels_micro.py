@@ -29,7 +29,7 @@ for l, (H, W) in enumerate(dims):
 
 
 def levels():
-    lib.adr_dcn_wgrad_bf16_levels(ctypes.cast(lv, ctypes.c_void_p), 3, C, 32, C, N, C, C, K.stream())
+    lib.adr_dcn_wgrad_bf16_levels(lv, 3, C, 32, C, N, C, C, K.stream())
 
 
 def per_level():

@@ -16,7 +16,7 @@ import weakref
 
 import torch
 
-from .native import ConvDesc, lib
+from .native import ConvDesc, lib, struct
 
 F32, BF16 = 0, 1
 ACT = {"none": 0, "silu": 1, "gelu": 2, "relu": 3, "sigmoid": 4, "hswish": 5}
@@ -124,21 +124,22 @@ _ALG_BYTES = {
     "adr_dwconv_bwd_fused": (lambda a: f"adr::dw_bwd_fused_kernel<__bf16, {a[13]}>",
                              lambda a: _es(a[0]) * a[9] * a[10] * a[11] * a[12] * (3 + a[14])
                              + 4 * a[12] * a[13] * a[13] * (a[9] + 1),
-                             lambda a: a[14] == 0 and not (_ptr(a[8]) and a[15])),
+                             lambda a: a[14] == 0 and not (_addr(a[8]) and a[15])),
     "adr_ew": ("adr::ew_kernel<__bf16>",
                lambda a: _es(a[0]) * a[11] * a[12] * (2 + (a[5] is not None) + (a[7] is not None) + a[15]),
-               lambda a: a[15] == 0 and _ptr(a[9]) not in (_ptr(a[3]), _ptr(a[5]), _ptr(a[7]))),
+               lambda a: a[15] == 0 and _addr(a[9]) not in (_addr(a[3]), _addr(a[5]), _addr(a[7]))),
 }
 
 
-def _ptr(v):
+def _addr(v):
+    """A device address as an int (or None): unwraps a ctypes.c_void_p, passes an int through."""
     return v.value if isinstance(v, ctypes.c_void_p) else v
 
 
-def _entries(args, struct):
+def _entries(args, entry_type):
     """The ctypes entry array a batched entry point was handed (args[0] = pointer, args[1] = count)."""
     n = int(args[1])
-    return ctypes.cast(args[0], ctypes.POINTER(struct))[:n] if n > 0 and _ptr(args[0]) else []
+    return ctypes.cast(args[0], ctypes.POINTER(entry_type))[:n] if n > 0 and _addr(args[0]) else []
 
 
 # batched entry points: algorithmic bytes summed over their entries (each entry's tensors touched once)
@@ -158,7 +159,7 @@ _BATCHED_BYTES = {
                                         for e in _entries(a, DotsumEntry)),
     "adr_copy_pieces": lambda a: sum(4 * int(a[2]) * e.C for e in _entries(a, CopyPiece)),
     # fp32 weights read once, both bf16 layouts written (PackCache._build records the sum per table)
-    "adr_pack_weight2_tiled": lambda a: _PACK_BYTES.get(_ptr(a[1]), 0),
+    "adr_pack_weight2_tiled": lambda a: _PACK_BYTES.get(_addr(a[1]), 0),
 }
 _PACK_BYTES = {}  # device table pointer -> algorithmic bytes of one adr_pack_weight2_tiled launch
 
@@ -181,7 +182,7 @@ def _generic_bytes(name, args):
     calling frames (the autograd Function that issued it). None when no pointer matched."""
     import sys
     types_ = lib.protos.get(name, (None, []))[1]
-    want = {_ptr(a) for a, t in zip(args, types_) if t is ctypes.c_void_p and _ptr(a)}
+    want = {_addr(a) for a, t in zip(args, types_) if t is ctypes.c_void_p and _addr(a)}
     if not want:
         return None
     found = {}
@@ -717,56 +718,50 @@ def pack_weight2(w: torch.Tensor, dtype, cpad: int = 0, transpose_kc: int = 0, k
     return krsc, crsk
 
 
-class WgradEntry(ctypes.Structure):
-    """adr_wgrad_reduce_entry (include/adr.h)."""
-    _fields_ = [("part", ctypes.c_void_p), ("dst", ctypes.c_void_p), ("split_stride", ctypes.c_long)] + [
-        (n, ctypes.c_int) for n in ("splits", "K", "C", "Cp", "RS", "transpose_kc", "accumulate", "pad_")]
+# include/adr.h's structures (parsed by native.py) under the names this module, the tests and the scripts use
+WgradEntry = struct("adr_wgrad_reduce_entry")
+WgradJob = struct("adr_wgrad_job")
+PsumEntry = struct("adr_psum_entry")
+ColsumEntry = struct("adr_colsum_entry")
+GnParamEntry = struct("adr_gnparam_entry")
+DotsumEntry = struct("adr_dotsum_entry")
+CopyPiece = struct("adr_copy_piece")
+AxpyEntry = struct("adr_axpy_entry")
+BStatStruct = struct("adr_bn_bstat")
+BnXfStruct = struct("adr_bnact_xf")
+DcnLevelStruct = struct("adr_dcn_level")
 
 
-class WgradJob(ctypes.Structure):
-    """adr_wgrad_job (include/adr.h)."""
-    _fields_ = [("d", ConvDesc), ("x", ctypes.c_void_p), ("dy", ctypes.c_void_p), ("out", ctypes.c_void_p),
-                ("accumulate", ctypes.c_int), ("pad_", ctypes.c_int), ("bias", ctypes.c_void_p)]
+def _launch_entries(fn, entries, *args, repeat=1):
+    """A batched entry point over a list of its ctypes entries: fn(entry array, count, *args, stream)."""
+    arr = (type(entries[0]) * len(entries))(*entries)
+    for _ in range(repeat):
+        fn(arr, len(entries), *args, stream())
 
 
-class PsumEntry(ctypes.Structure):
-    """adr_psum_entry (include/adr.h)."""
-    _fields_ = [("partial", ctypes.c_void_p), ("out", ctypes.c_void_p)] + [
-        (n, ctypes.c_int) for n in ("P", "C", "which", "accumulate")]
+class _Queue:
+    """One kind of deferred launch: the batched entry point that drains it, its entries and what they keep alive.
+    An entry added with a destination (a device address) that is already queued calls on_repeat first (the owner's
+    flush, which clears the queue), so a destination's contributions accumulate in program order."""
 
+    def __init__(self, fn, on_repeat=None):
+        self.fn, self.on_repeat = fn, on_repeat
+        self.clear()
 
-class ColsumEntry(ctypes.Structure):
-    """adr_colsum_entry (include/adr.h)."""
-    _fields_ = [("x", ctypes.c_void_p), ("partial", ctypes.c_void_p)] + [
-        (n, ctypes.c_int) for n in ("xcs", "N", "HW", "C", "rows_per_chunk", "chunks")]
+    def clear(self):
+        self.entries, self.keep, self.dsts = [], [], set()
 
+    def add(self, entry, keep, dst=None):
+        if dst is not None:
+            if dst in self.dsts:
+                self.on_repeat()
+            self.dsts.add(dst)
+        self.entries.append(entry)
+        self.keep += keep
 
-class GnParamEntry(ctypes.Structure):
-    """adr_gnparam_entry (include/adr.h)."""
-    _fields_ = [(n, ctypes.c_void_p) for n in ("partial", "mean", "rstd", "dgamma", "dbeta")] + [
-        (n, ctypes.c_int) for n in ("N", "chunks", "C", "G", "accumulate", "pad_")]
-
-
-class DotsumEntry(ctypes.Structure):
-    """adr_dotsum_entry (include/adr.h)."""
-    _fields_ = [(n, ctypes.c_void_p) for n in ("x", "dz", "partial", "out")] + [
-        (n, ctypes.c_int) for n in ("xcs", "dcs", "N", "HW", "C", "rows_per_chunk", "chunks", "pad_")]
-
-
-class CopyPiece(ctypes.Structure):
-    """adr_copy_piece (include/adr.h)."""
-    _fields_ = [("src", ctypes.c_void_p), ("dst", ctypes.c_void_p)] + [
-        (n, ctypes.c_int) for n in ("scs", "dcs", "C", "pad_")]
-
-
-class AxpyEntry(ctypes.Structure):
-    """adr_axpy_entry (include/adr.h)."""
-    _fields_ = [("x", ctypes.c_void_p), ("y", ctypes.c_void_p), ("n", ctypes.c_long)]
-
-
-def _nullctx():
-    import contextlib
-    return contextlib.nullcontext()
+    def drain(self):
+        if self.entries:
+            _launch_entries(self.fn, self.entries)
 
 
 class WgradDeferral:
@@ -777,13 +772,19 @@ class WgradDeferral:
     destination's contributions still accumulate in program order."""
 
     def __init__(self):
-        self.jobs, self.jkeep, self.jwork = [], [], []  # deferred WGRAD partial launches
-        self.entries, self.keep, self.dsts = [], [], set()
-        self.psums, self.pkeep, self.pdsts = [], [], set()
-        self.axpys, self.akeep, self.adsts = [], [], set()
-        self.cols, self.ckeep = [], []
-        self.gnps, self.gkeep = [], []
-        self.dots, self.dkeep = [], []
+        self.jobs = _Queue(lib.adr_conv2d_wgrad_partials_batched)  # deferred WGRAD partial launches
+        self.dots = _Queue(lib.adr_dotsum_batched)
+        self.cols = _Queue(lib.adr_nc_reduce_batched)
+        self.reduces = _Queue(lib.adr_wgrad_reduce_batched, self.flush)
+        self.psums = _Queue(lib.adr_partial_sum_batched, self.flush)
+        self.axpys = _Queue(lib.adr_axpy_batched, self.flush)
+        self.gnps = _Queue(lib.adr_gn_param_grad_batched)
+        self._clear()
+
+    def _clear(self):
+        for q in (self.jobs, self.dots, self.cols, self.reduces, self.psums, self.axpys, self.gnps):
+            q.clear()
+        self.jwork = []  # (algorithmic work, shape label) per job, for the timed flush
         self.post_dots = []  # callables run right after the batched dot sums (they consume their outputs)
 
     def add_dotsum(self, x, dy, out):
@@ -796,16 +797,13 @@ class WgradDeferral:
         part = torch.empty(N * chunks * 2 * C, dtype=torch.float32, device=dy.device)
         vd[0]._adr_pinned = True
         dy._adr_pinned = True
-        self.dots.append(DotsumEntry(vx[1], vd[1], part.data_ptr(), out.data_ptr(), vx[2], vd[2], N, H * W, C, rows,
-                                     chunks, 0))
-        self.dkeep += [vx[0], vd[0], part, out]
+        self.dots.add(DotsumEntry(vx[1], vd[1], part.data_ptr(), out.data_ptr(), vx[2], vd[2], N, H * W, C, rows,
+                                  chunks, 0), [vx[0], vd[0], part, out])
 
     def add_gnparam(self, part, mean, rstd, pg, pb, N, chunks, C, G, acc):
         """A GroupNorm dgamma / dbeta reduction (arena destinations), batched at the flush."""
-        val = lambda q: q.value if isinstance(q, ctypes.c_void_p) else q  # noqa: E731
-        self.gnps.append(GnParamEntry(part.data_ptr(), mean.data_ptr(), rstd.data_ptr(), val(pg), val(pb), N, chunks,
-                                      C, G, acc, 0))
-        self.gkeep += [part, mean, rstd]
+        self.gnps.add(GnParamEntry(part.data_ptr(), mean.data_ptr(), rstd.data_ptr(), _addr(pg), _addr(pb), N, chunks,
+                                   C, G, acc, 0), [part, mean, rstd])
 
     def add_colsum(self, x, part, xcs, N, HW, C, rows, chunks):
         """A bias gradient's column sums (adr_nc_reduce RED_STATS of dy into `part`), run in one batched launch
@@ -813,27 +811,15 @@ class WgradDeferral:
         fan-out sum accumulates into it in place before the flush reads it."""
         x._adr_pinned = True
         _v(x)[0]._adr_pinned = True
-        self.cols.append(ColsumEntry(x.data_ptr(), part.data_ptr(), xcs, N, HW, C, rows, chunks))
-        self.ckeep.append(x)
-        self.ckeep.append(part)
+        self.cols.add(ColsumEntry(x.data_ptr(), part.data_ptr(), xcs, N, HW, C, rows, chunks), [x, part])
 
     def add_axpy(self, src, dst, n):
         """A parameter gradient computed into a temporary, to be added into the arena (sink)."""
-        dst = dst.value if isinstance(dst, ctypes.c_void_p) else int(dst)
-        if dst in self.adsts:
-            self.flush()
-        self.axpys.append(AxpyEntry(src.data_ptr(), dst, n))
-        self.akeep.append(src)
-        self.adsts.add(dst)
+        self.axpys.add(AxpyEntry(src.data_ptr(), _addr(dst), n), [src], _addr(dst))
 
     def add_psum(self, part, P, C, which, dst, acc):
         """A bias gradient (adr_partial_sum into the arena), batched the same way."""
-        dst = dst.value if isinstance(dst, ctypes.c_void_p) else int(dst)
-        if dst in self.pdsts:
-            self.flush()
-        self.psums.append(PsumEntry(part.data_ptr(), dst, P, C, which, acc))
-        self.pkeep.append(part)
-        self.pdsts.add(dst)
+        self.psums.add(PsumEntry(part.data_ptr(), _addr(dst), P, C, which, acc), [part], _addr(dst))
 
     def add_job(self, d, xp, dyp, ws, keep, work=(0, 0), shp="", bias=None):
         """A conv's WGRAD partials into `ws`, launched at the flush together with the stage's other weight gradients
@@ -843,21 +829,14 @@ class WgradDeferral:
             if torch.is_tensor(t):
                 t._adr_pinned = True
                 _v(t)[0]._adr_pinned = True
-        self.jobs.append(WgradJob(ConvDesc.from_buffer_copy(d), xp, dyp, ws.data_ptr(), 0, 0,
-                                  bias.data_ptr() if bias is not None else None))
+        self.jobs.add(WgradJob(ConvDesc.from_buffer_copy(d), xp, dyp, ws.data_ptr(), 0, 0,
+                               bias.data_ptr() if bias is not None else None),
+                      [ws, *keep] + ([bias] if bias is not None else []))
         self.jwork.append((work, shp))
-        self.jkeep += [ws, *keep] + ([bias] if bias is not None else [])
 
     def add(self, ws, stride, splits, dst, K_, C_, Cp, RS_, transpose_kc, acc):
-        dst = dst.value if isinstance(dst, ctypes.c_void_p) else int(dst)
-        if dst in self.dsts:
-            self.flush()
-        self.entries.append(WgradEntry(ws.data_ptr(), dst, stride, splits, K_, C_, Cp, RS_, transpose_kc, acc, 0))
-        self.keep.append(ws)
-        self.dsts.add(dst)
-
-    def flush(self):
-        self._flush()
+        self.reduces.add(WgradEntry(ws.data_ptr(), _addr(dst), stride, splits, K_, C_, Cp, RS_, transpose_kc, acc, 0),
+                         [ws], _addr(dst))
 
     def _timed_jobs(self):
         """bench.py's roofline timing: the same grouped launches the step makes (one per tile shape, at most
@@ -865,7 +844,7 @@ class WgradDeferral:
         algorithmic bytes / flops of its jobs; thin / halo jobs (their own kernels) one call each. The partial
         writes are idempotent, so each call repeats TIMING_REPEAT times inside its event pair."""
         groups = {}
-        for job, (work, shp) in zip(self.jobs, self.jwork):
+        for job, (work, shp) in zip(self.jobs.entries, self.jwork):
             tile = lib.adr_conv2d_wgrad_batched_tile(ctypes.byref(job.d))
             groups.setdefault(tile, []).append((job, work, shp))
         for tile, items in groups.items():
@@ -876,48 +855,33 @@ class WgradDeferral:
                         else "adr_conv2d_wgrad (thin / 3x3 halo kernel)")
                 nb = sum(w[0] for _, w, _ in part)
                 fl = sum(w[1] for _, w, _ in part)
-                arr = (WgradJob * len(part))(*[j for j, _, _ in part])
                 rep = TIMING_REPEAT
                 tok = _t0(name, nb, fl, " + ".join(sh for _, _, sh in part), rep)
-                for _ in range(rep):
-                    lib.adr_conv2d_wgrad_partials_batched(ctypes.cast(arr, ctypes.c_void_p), len(part), stream())
+                _launch_entries(self.jobs.fn, [j for j, _, _ in part], repeat=rep)
                 _t1(tok)
 
-    def _flush(self):
-        if self.jobs:  # the deferred weight-gradient partials, before their reductions
-            if _TIMING is None:
-                arr = (WgradJob * len(self.jobs))(*self.jobs)
-                lib.adr_conv2d_wgrad_partials_batched(ctypes.cast(arr, ctypes.c_void_p), len(self.jobs), stream())
-            else:
-                self._timed_jobs()
-            self.jobs, self.jkeep, self.jwork = [], [], []
-        if self.dots:  # before the axpys that add their outputs into the arena
-            arr = (DotsumEntry * len(self.dots))(*self.dots)
-            lib.adr_dotsum_batched(ctypes.cast(arr, ctypes.c_void_p), len(self.dots), stream())
+    def _drain_jobs(self):
+        if _TIMING is None:
+            self.jobs.drain()
+        elif self.jobs.entries:
+            self._timed_jobs()
+
+    def _run_post_dots(self):
         for fn in self.post_dots:
             fn()
-        if self.cols:  # before the partial sums that read their rows
-            arr = (ColsumEntry * len(self.cols))(*self.cols)
-            lib.adr_nc_reduce_batched(ctypes.cast(arr, ctypes.c_void_p), len(self.cols), stream())
-        if self.entries:
-            arr = (WgradEntry * len(self.entries))(*self.entries)
-            lib.adr_wgrad_reduce_batched(ctypes.cast(arr, ctypes.c_void_p), len(self.entries), stream())
-        if self.psums:
-            arr = (PsumEntry * len(self.psums))(*self.psums)
-            lib.adr_partial_sum_batched(ctypes.cast(arr, ctypes.c_void_p), len(self.psums), stream())
-        if self.axpys:
-            arr = (AxpyEntry * len(self.axpys))(*self.axpys)
-            lib.adr_axpy_batched(ctypes.cast(arr, ctypes.c_void_p), len(self.axpys), stream())
-        if self.gnps:
-            arr = (GnParamEntry * len(self.gnps))(*self.gnps)
-            lib.adr_gn_param_grad_batched(ctypes.cast(arr, ctypes.c_void_p), len(self.gnps), stream())
-        self.entries, self.keep, self.dsts = [], [], set()
-        self.psums, self.pkeep, self.pdsts = [], [], set()
-        self.axpys, self.akeep, self.adsts = [], [], set()
-        self.cols, self.ckeep = [], []
-        self.gnps, self.gkeep = [], []
-        self.dots, self.dkeep = [], []
-        self.post_dots = []
+
+    def flush(self):
+        """Everything pending, in the order the data flows."""
+        for step in (self._drain_jobs,      # the weight-gradient partials, before their reductions
+                     self.dots.drain,       # scalar dot sums, before the axpys that add their outputs into the arena
+                     self._run_post_dots,
+                     self.cols.drain,       # bias column sums, before the partial sums that read their rows
+                     self.reduces.drain,
+                     self.psums.drain,
+                     self.axpys.drain,
+                     self.gnps.drain):
+            step()
+        self._clear()
 
 
 def _defer_dot(param, x, dy):
@@ -1471,12 +1435,6 @@ def bnxf_clear():
 BN_BSTAT = True  # 0: adr_nc_reduce's backward pass over dz and y; reference of tests/test_gpu_bstat.py
 
 
-class BStatStruct(ctypes.Structure):
-    """adr_bn_bstat (include/adr.h)."""
-    _fields_ = [("y", ctypes.c_void_p), ("scale", ctypes.c_void_p), ("shift", ctypes.c_void_p),
-                ("y_cstride", ctypes.c_int), ("act", ctypes.c_int)]
-
-
 class BnStat:
     """A training BN-act's backward statistics, taken from its only reader's data gradient: (y, scale, shift, act)
     from the forward; after that dgrad, the partials and the identity (address, geometry, version) of the dz
@@ -1509,12 +1467,6 @@ class BnStat:
         got = (self.part, self.P) if ok else None
         self.part = self.P = self.key = self.ref = None
         return got
-
-
-class BnXfStruct(ctypes.Structure):
-    """adr_bnact_xf (include/adr.h)."""
-    _fields_ = [(n, ctypes.c_void_p) for n in ("y", "scale", "shift", "A", "B", "Cc", "out")] + [
-        (n, ctypes.c_int) for n in ("y_cstride", "out_cstride", "act", "pad_")]
 
 
 class BnXf:
@@ -1973,8 +1925,8 @@ class CatFn(torch.autograd.Function):
         if len(todo) > 1 and _TIMING is None and t0.dtype == torch.bfloat16 and all(
                 c % 8 == 0 and v[2] % 8 == 0 and v[1] % 16 == 0 and o.data_ptr() % 16 == 0 for o, v, c in todo):
             # every piece that needs a copy in one launch (adr_copy_pieces; bitwise the per-piece copies)
-            arr = (CopyPiece * len(todo))(*[CopyPiece(v[1], o.data_ptr(), v[2], Ctot, c, 0) for o, v, c in todo])
-            lib.adr_copy_pieces(ctypes.cast(arr, ctypes.c_void_p), len(todo), N * H * W, stream())
+            _launch_entries(lib.adr_copy_pieces, [CopyPiece(v[1], o.data_ptr(), v[2], Ctot, c, 0) for o, v, c in todo],
+                            N * H * W)
         else:
             for o, v, _ in todo:
                 _ew(EW_COPY, (o, o.data_ptr(), Ctot), v)
@@ -2963,12 +2915,6 @@ def _dcn_far_scratch_levels(dev, N, dims, C):
         out.append((f[o:o + k], g[ot:ot + kt]))
         o, ot = o + k, ot + kt
     return out
-
-
-class DcnLevelStruct(ctypes.Structure):
-    """adr_dcn_level (include/adr.h)."""
-    _fields_ = [(n, ctypes.c_void_p) for n in ("x", "om", "dy", "y", "dx", "dom", "dxf", "flags", "part")] + [
-        (n, ctypes.c_int) for n in ("H", "W", "splits", "pad_")]
 
 
 # the AYHead's DCN levels in one launch per direction (adr_dcn_*_bf16_levels)
@@ -4001,10 +3947,8 @@ class GNPackFn(torch.autograd.Function):
             if _defer_gn(acc_g):
                 _dfr().add_gnparam(pv, mv, rv, pg, pb, n, chunks, C, groups, acc_g)
             else:
-                val = lambda q: q.value if isinstance(q, ctypes.c_void_p) else q  # noqa: E731
-                arr = (GnParamEntry * 1)(GnParamEntry(pv.data_ptr(), mv.data_ptr(), rv.data_ptr(), val(pg), val(pb),
-                                                      n, chunks, C, groups, acc_g, 0))
-                lib.adr_gn_param_grad_batched(ctypes.cast(arr, ctypes.c_void_p), 1, stream())
+                _launch_entries(lib.adr_gn_param_grad_batched, [GnParamEntry(
+                    pv.data_ptr(), mv.data_ptr(), rv.data_ptr(), _addr(pg), _addr(pb), n, chunks, C, groups, acc_g, 0)])
             grads[j], grads[nl + j] = grad_ret(gam, dgamma), grad_ret(bet, dbeta)
         return (dy, None, None, None, None, None, *grads)
 
@@ -4235,7 +4179,7 @@ class LevelDCNFn(torch.autograd.Function):
             tok = _t0("adr::dcn_fwd_levels_kernel(adr::DcnLevels)", *work,
                       f"dcn fwd levels n{N} {pack.dims} c{C}->{Cout}" if _TIMING is not None else "", _reps())
             for _ in range(_reps()):
-                lib.adr_dcn_fwd_bf16_levels(ctypes.cast(lv, ctypes.c_void_p), len(pack.dims), xcs, omcs, fptr(wp),
+                lib.adr_dcn_fwd_bf16_levels(lv, len(pack.dims), xcs, omcs, fptr(wp),
                                             Cout, N, C, Cout, stream())
             _t1(tok)
             ctx.save_for_backward(x, om, w)
@@ -4301,7 +4245,7 @@ class LevelDCNFn(torch.autograd.Function):
             nb = sum(w_[0] + 2 * N * H * W * C for w_, (H, W) in zip(works, pack.dims))
             tok = _t0("adr::dcn_bwd_levels_kernel(adr::DcnLevels)", nb, 2 * sum(w_[1] for w_ in works),
                       f"dcn bwd levels n{N} {pack.dims} c{C}->{Cout}" if _TIMING is not None else "")
-            lib.adr_dcn_bwd_bf16_levels(ctypes.cast(lv, ctypes.c_void_p), len(pack.dims), xcs, omcs, dycs, fptr(wt),
+            lib.adr_dcn_bwd_bf16_levels(lv, len(pack.dims), xcs, omcs, dycs, fptr(wt),
                                         C, omc, N, C, Cout, stream())
             _t1(tok)
             if ctx.needs_input_grad[2]:
@@ -4315,7 +4259,7 @@ class LevelDCNFn(torch.autograd.Function):
                 tok = _t0("adr::dcn_wgrad_levels_kernel(adr::DcnLevels)",
                           sum(w_[0] for w_ in works) + 4 * s0 * stride, sum(w_[1] for w_ in works),
                           f"dcn wgrad levels/{s0} n{N} {pack.dims} c{C}->{Cout}" if _TIMING is not None else "")
-                lib.adr_dcn_wgrad_bf16_levels(ctypes.cast(lv, ctypes.c_void_p), len(pack.dims), xcs, omcs, dycs, N, C,
+                lib.adr_dcn_wgrad_bf16_levels(lv, len(pack.dims), xcs, omcs, dycs, N, C,
                                               Cout, stream())
                 _t1(tok)
                 out, ptr, acc = grad_dst(ctx.pw, stride, dev)

@@ -1,5 +1,6 @@
-"""ctypes binding of libadr_hip.so. Prototypes are parsed from include/adr.h so the Python view of the ABI
-cannot drift from the header. Every call checks the status and raises RuntimeError(adr_last_error())."""
+"""ctypes binding of libadr_hip.so. Prototypes and every `typedef struct` are parsed from include/adr.h, so the
+Python view of the ABI (argument types, structure layouts) cannot drift from the header; tests/test_abi.py checks the
+parsed layouts against the C compiler's. Every call checks the status and raises RuntimeError(adr_last_error())."""
 from __future__ import annotations
 
 import ctypes
@@ -14,13 +15,7 @@ if not HEADER.exists():  # installed layout: header shipped next to the library
     HEADER = _HERE / "lib" / "adr.h"
 
 
-class ConvDesc(ctypes.Structure):
-    _fields_ = [(n, ctypes.c_int) for n in (
-        "n", "h", "w", "c", "x_cstride", "x_coff", "k", "r", "s", "stride_h", "stride_w", "pad_h", "pad_w",
-        "ho", "wo", "y_cstride", "y_coff", "dtype")]
-
-
-_STRUCTS = {"adr_conv_desc": ConvDesc}
+_STRUCTS = {}  # adr.h typedef name -> ctypes.Structure (filled by parse_header; struct() looks one up)
 
 
 def _ctype(t: str):
@@ -33,13 +28,30 @@ def _ctype(t: str):
         if base == "char":
             return ctypes.c_char_p
         return ctypes.c_void_p
+    if base in _STRUCTS:
+        return _STRUCTS[base]
     return {"int": ctypes.c_int, "double": ctypes.c_double, "float": ctypes.c_float, "size_t": ctypes.c_size_t,
             "long": ctypes.c_long, "uint8_t": ctypes.c_uint8, "int64_t": ctypes.c_int64, "void": None}[base]
+
+
+def _struct(name, body):
+    """The ctypes.Structure of one `typedef struct { type a, b[4]; ... } name;` body (pointers are c_void_p)."""
+    fields = []
+    for decl in filter(None, (d.strip() for d in body.split(";"))):
+        t, first = re.match(r"(.*?)(\w+(?:\[\d+\])?)$", decl.split(",")[0].strip()).groups()
+        for f in [first] + [n.strip() for n in decl.split(",")[1:]]:
+            m = re.match(r"(\w+)(?:\[(\d+)\])?$", f)
+            ct = _ctype(t)
+            fields.append((m.group(1), ct * int(m.group(2)) if m.group(2) else ct))
+    return type(name, (ctypes.Structure,), {"_fields_": fields, "__doc__": f"{name} (include/adr.h)"})
 
 
 def parse_header(path=HEADER):
     src = path.read_text()
     src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
+    for m in re.finditer(r"typedef\s+struct\s*\w*\s*\{(.*?)\}\s*(adr_\w+)\s*;", src, re.S):
+        if m.group(2) not in _STRUCTS:  # in header order: a nested struct is declared before its user
+            _STRUCTS[m.group(2)] = _struct(m.group(2), m.group(1))
     protos = {}
     for m in re.finditer(r"^\s*((?:const\s+)?[a-z_0-9]+\s*\**)\s*(adr_[a-z0-9_]+)\s*\(([^)]*)\)\s*;", src, re.M):
         ret, name, args = m.group(1), m.group(2), m.group(3)
@@ -128,4 +140,12 @@ _NONSTATUS = {"adr_abi_version", "adr_conv2d_wgrad_bias_fusable", "adr_dwconv_wg
 _ = _NONSTATUS
 
 lib = _Lib()
+
+
+def struct(name):
+    """The ctypes.Structure parsed from include/adr.h's `typedef struct ... name;`."""
+    return _STRUCTS[name]
+
+
+ConvDesc = struct("adr_conv_desc")
 assert lib.lib.adr_abi_version() == 1, "ABI version mismatch"

@@ -4,6 +4,7 @@
 #include <hip/hip_bf16.h>
 #include <stdint.h>
 #include <stddef.h>
+#include <type_traits>
 #include "../../include/adr.h"
 
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
@@ -337,6 +338,70 @@ __device__ __forceinline__ float wave_sum_dpp(float v) {
 __device__ __forceinline__ double wave_sum_d(double v) {
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
   return v;
+}
+
+// ---- batched launches: many small jobs of one kind in ONE launch (the deferred parameter-gradient flush) ----
+// The entries ride in the kernel arguments; block b of the grid belongs to entry j, start[j] <= b < start[j + 1].
+// Each kernel names its own derived struct (the name is part of the kernel's signature, which profiles record).
+template <class E, int MAX>
+struct Batch {
+  static constexpr int cap = MAX;
+  E e[MAX];
+  int start[MAX + 1];
+  int count;
+};
+
+// device: the block's entry and its index within that entry (a linear scan: a batch holds at most a few dozen)
+struct BatchBlock {
+  int j, local;
+};
+template <class B>
+__device__ __forceinline__ BatchBlock batch_block(const B& b) {
+  int j = 0;
+  while (j + 1 < b.count && (int)blockIdx.x >= b.start[j + 1]) ++j;
+  return {j, (int)blockIdx.x - b.start[j]};
+}
+
+// host: what happens when an entry writes a destination an earlier entry of the same launch writes
+enum class DupDst {
+  None,    // not looked at (the entries cannot collide, or only read)
+  Reject,  // ADR_ERR_BAD_ARG: the caller must not batch them
+  Split,   // the launch ends before the entry; it opens the next one, so the two accumulate in entry order
+};
+
+// host: cut `count` entries into batches B of at most B::cap and launch each. entry(e, index, blocks) validates the
+// copy e of entries[index] (and may edit it), sets its block count and returns a status (ADR_REQUIRE inside it
+// returns from the callable; the status is passed on). launch(b, blocks) launches one filled batch; a batch
+// without blocks is skipped. same_dst(a, b), given with a policy Reject or Split, tells whether two entries share
+// a destination.
+template <class B, class E, class Entry, class Launch, class SameDst = std::nullptr_t>
+int launch_batches(const char* who, const E* entries, int count, Entry entry, Launch launch,
+                   DupDst dup = DupDst::None, SameDst same_dst = nullptr) {
+  ADR_REQUIRE(count >= 0 && (count == 0 || entries), "%s: count=%d", who, count);
+  for (int b0 = 0; b0 < count;) {
+    B b{};
+    long blocks = 0;
+    int j = 0;
+    for (; j < B::cap && b0 + j < count; ++j) {
+      b.e[j] = entries[b0 + j];
+      long nb = 0;
+      if (const int rc = entry(b.e[j], b0 + j, nb)) return rc;
+      if constexpr (!std::is_same_v<SameDst, std::nullptr_t>) {
+        int q = 0;
+        while (q < j && !same_dst(b.e[q], b.e[j])) ++q;
+        if (q < j && dup == DupDst::Split) break;
+        ADR_REQUIRE(q == j, "%s: entries %d and %d share a destination", who, b0 + q, b0 + j);
+      }
+      b.start[j] = (int)blocks;
+      blocks += nb;
+    }
+    ADR_REQUIRE(blocks < (1l << 31), "%s: grid of %ld blocks", who, blocks);
+    b.count = j;
+    b.start[j] = (int)blocks;
+    if (blocks) launch(b, (unsigned)blocks);
+    b0 += j;
+  }
+  return check_launch(who);
 }
 
 }  // namespace adr

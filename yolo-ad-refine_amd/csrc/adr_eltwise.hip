@@ -238,16 +238,11 @@ __global__ void __launch_bounds__(256) dot_reduce_kernel(const T* __restrict__ x
 // entry), then one 1024-thread workgroup per entry collapsing its partial rows — the same bodies, so the same
 // fixed summation order as adr_dot_reduce + adr_nc_collapse(sum_n = sum_c = 1).
 constexpr int DTB_MAX = 32;
-struct DotBatch {
-  adr_dotsum_entry e[DTB_MAX];
-  int start[DTB_MAX + 1];
-  int count;
-};
+struct DotBatch : Batch<adr_dotsum_entry, DTB_MAX> {};
 __global__ void __launch_bounds__(256) dot_reduce_batched_kernel(DotBatch b) {
-  int j = 0;
-  while (j + 1 < b.count && (int)blockIdx.x >= b.start[j + 1]) ++j;
-  const adr_dotsum_entry& en = b.e[j];
-  const int local = (int)blockIdx.x - b.start[j];
+  const BatchBlock bb = batch_block(b);
+  const adr_dotsum_entry& en = b.e[bb.j];
+  const int local = bb.local;
   dot_reduce_body<__bf16>((const __bf16*)en.x, en.xcs, (const __bf16*)en.dz, en.dcs, en.HW, en.C, en.rows_per_chunk,
                           en.chunks, en.partial, local % en.chunks, local / en.chunks);
 }
@@ -284,16 +279,11 @@ __global__ void axpy_kernel(long n, float a, const float* x, float* y) {
 // Many y += x over distinct destinations in one launch (the trainer's deferred parameter-gradient adds): 1024
 // elements per workgroup, the entry found from the per-entry block offsets.
 constexpr int AXB_MAX = 96;
-struct AxpyBatch {
-  adr_axpy_entry e[AXB_MAX];
-  int start[AXB_MAX + 1];
-  int count;
-};
+struct AxpyBatch : Batch<adr_axpy_entry, AXB_MAX> {};
 __global__ void __launch_bounds__(256) axpy_batched_kernel(AxpyBatch b) {
-  int j = 0;
-  while (j + 1 < b.count && (int)blockIdx.x >= b.start[j + 1]) ++j;
-  const adr_axpy_entry& en = b.e[j];
-  const long base = (long)(blockIdx.x - b.start[j]) * 1024 + threadIdx.x;
+  const BatchBlock bb = batch_block(b);
+  const adr_axpy_entry& en = b.e[bb.j];
+  const long base = (long)(unsigned)bb.local * 1024 + threadIdx.x;
 #pragma unroll
   for (int u = 0; u < 4; ++u) {
     const long i = base + u * 256;
@@ -367,28 +357,20 @@ extern "C" int adr_dot_reduce(int dtype, const void* x, int xcs, const void* dz,
 }
 
 extern "C" int adr_dotsum_batched(const adr_dotsum_entry* entries, int count, void* stream) {
-  ADR_REQUIRE(count >= 0 && (count == 0 || entries), "dotsum_batched: count=%d", count);
-  hipStream_t st = (hipStream_t)stream;
-  for (int b0 = 0; b0 < count; b0 += DTB_MAX) {
-    DotBatch db{};
-    db.count = count - b0 < DTB_MAX ? count - b0 : DTB_MAX;
-    long blocks = 0;
-    for (int j = 0; j < db.count; ++j) {
-      const adr_dotsum_entry& en = entries[b0 + j];
-      ADR_REQUIRE(en.x && en.dz && en.partial && en.out && en.N > 0 && en.HW > 0 && en.C % 8 == 0 &&
-                      en.C / 8 <= 256 && en.xcs % 8 == 0 && en.dcs % 8 == 0 && en.rows_per_chunk > 0 &&
-                      en.chunks == cdiv(en.HW, en.rows_per_chunk),
-                  "dotsum_batched: entry %d", b0 + j);
-      db.e[j] = en;
-      db.start[j] = (int)blocks;
-      blocks += (long)en.N * en.chunks;
-    }
-    ADR_REQUIRE(blocks < (1l << 31), "dotsum_batched: grid");
-    db.start[db.count] = (int)blocks;
-    hipLaunchKernelGGL(dot_reduce_batched_kernel, dim3((unsigned)blocks), dim3(256), 0, st, db);
-    hipLaunchKernelGGL(dot_collapse_batched_kernel, dim3(db.count), dim3(1024), 0, st, db);
-  }
-  return check_launch("adr_dotsum_batched");
+  return launch_batches<DotBatch>(
+      "adr_dotsum_batched", entries, count,
+      [](adr_dotsum_entry& en, int i, long& blocks) -> int {
+        ADR_REQUIRE(en.x && en.dz && en.partial && en.out && en.N > 0 && en.HW > 0 && en.C % 8 == 0 &&
+                        en.C / 8 <= 256 && en.xcs % 8 == 0 && en.dcs % 8 == 0 && en.rows_per_chunk > 0 &&
+                        en.chunks == cdiv(en.HW, en.rows_per_chunk),
+                    "dotsum_batched: entry %d", i);
+        blocks = (long)en.N * en.chunks;
+        return ADR_OK;
+      },
+      [&](const DotBatch& b, unsigned blocks) {
+        hipLaunchKernelGGL(dot_reduce_batched_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, b);
+        hipLaunchKernelGGL(dot_collapse_batched_kernel, dim3(b.count), dim3(1024), 0, (hipStream_t)stream, b);
+      });
 }
 
 extern "C" int adr_nc_collapse(const float* partial, int N, int chunks, int C, int which, float* out, int sum_n,
@@ -417,42 +399,30 @@ extern "C" int adr_fusion_weights_bwd(const float* fw, int n, float eps, const f
 }
 
 extern "C" int adr_axpy_batched(const adr_axpy_entry* entries, int count, void* stream) {
-  ADR_REQUIRE(count >= 0 && (count == 0 || entries), "axpy_batched: count=%d", count);
-  for (int b0 = 0; b0 < count; b0 += AXB_MAX) {
-    AxpyBatch ab{};
-    ab.count = count - b0 < AXB_MAX ? count - b0 : AXB_MAX;
-    long blocks = 0;
-    for (int j = 0; j < ab.count; ++j) {
-      const adr_axpy_entry& en = entries[b0 + j];
-      ADR_REQUIRE(en.x && en.y && en.n > 0, "axpy_batched: entry %d", b0 + j);
-      for (int q = 0; q < j; ++q)
-        ADR_REQUIRE(ab.e[q].y != en.y, "axpy_batched: entries %d and %d share a destination", b0 + q, b0 + j);
-      ab.e[j] = en;
-      ab.start[j] = (int)blocks;
-      blocks += cdiv(en.n, 1024);
-    }
-    ADR_REQUIRE(blocks < (1l << 31), "axpy_batched: too many elements");
-    ab.start[ab.count] = (int)blocks;
-    hipLaunchKernelGGL(axpy_batched_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, ab);
-  }
-  return check_launch("adr_axpy_batched");
+  return launch_batches<AxpyBatch>(
+      "adr_axpy_batched", entries, count,
+      [](adr_axpy_entry& en, int i, long& blocks) -> int {
+        ADR_REQUIRE(en.x && en.y && en.n > 0, "axpy_batched: entry %d", i);
+        blocks = cdiv(en.n, 1024);
+        return ADR_OK;
+      },
+      [&](const AxpyBatch& b, unsigned blocks) {
+        hipLaunchKernelGGL(axpy_batched_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, b);
+      },
+      DupDst::Reject, [](const adr_axpy_entry& a, const adr_axpy_entry& en) { return a.y == en.y; });
 }
 
 
 constexpr int CPB_MAX = 8;
-struct CopyBatch {
-  adr_copy_piece e[CPB_MAX];
-  int start[CPB_MAX + 1];
-  int count;
+struct CopyBatch : Batch<adr_copy_piece, CPB_MAX> {
   unsigned npix;
 };
 // block b belongs to piece j (start[j] <= b < start[j+1]); a thread moves one 16-byte chunk (8 bf16 channels)
 __global__ void __launch_bounds__(256) copy_pieces_kernel(CopyBatch b) {
-  int j = 0;
-  while (j + 1 < b.count && (int)blockIdx.x >= b.start[j + 1]) ++j;
-  const adr_copy_piece& en = b.e[j];
+  const BatchBlock bb = batch_block(b);
+  const adr_copy_piece& en = b.e[bb.j];
   const unsigned c8 = (unsigned)en.C / 8u;
-  const unsigned i = (unsigned)(blockIdx.x - b.start[j]) * 256u + threadIdx.x;
+  const unsigned i = (unsigned)bb.local * 256u + threadIdx.x;
   if (i >= b.npix * c8) return;
   const unsigned pix = i / c8, c = (i - pix * c8) * 8u;
   st16(reinterpret_cast<__bf16*>(en.dst) + (size_t)pix * en.dcs + c,
@@ -460,27 +430,21 @@ __global__ void __launch_bounds__(256) copy_pieces_kernel(CopyBatch b) {
 }
 
 extern "C" int adr_copy_pieces(const adr_copy_piece* pieces, int count, long npix, void* stream) {
-  ADR_REQUIRE(count >= 0 && (count == 0 || pieces) && npix >= 0 && npix < (1l << 31), "copy_pieces: count=%d npix=%ld",
-              count, npix);
-  for (int b0 = 0; b0 < count; b0 += CPB_MAX) {
-    CopyBatch cb{};
-    cb.count = count - b0 < CPB_MAX ? count - b0 : CPB_MAX;
-    cb.npix = (unsigned)npix;
-    long blocks = 0;
-    for (int j = 0; j < cb.count; ++j) {
-      const adr_copy_piece& en = pieces[b0 + j];
-      ADR_REQUIRE(en.src && en.dst && en.C > 0 && en.C % 8 == 0 && en.scs % 8 == 0 && en.dcs % 8 == 0 &&
-                      ((uintptr_t)en.src & 15) == 0 && ((uintptr_t)en.dst & 15) == 0 && npix * (en.C / 8) < (1l << 31),
-                  "copy_pieces: piece %d (C=%d scs=%d dcs=%d)", b0 + j, en.C, en.scs, en.dcs);
-      cb.e[j] = en;
-      cb.start[j] = (int)blocks;
-      blocks += cdiv(npix * (en.C / 8), 256);
-    }
-    ADR_REQUIRE(blocks < (1l << 31), "copy_pieces: grid");
-    cb.start[cb.count] = (int)blocks;
-    if (blocks) hipLaunchKernelGGL(copy_pieces_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, cb);
-  }
-  return check_launch("adr_copy_pieces");
+  ADR_REQUIRE(npix >= 0 && npix < (1l << 31), "copy_pieces: npix=%ld", npix);
+  return launch_batches<CopyBatch>(
+      "adr_copy_pieces", pieces, count,
+      [&](adr_copy_piece& en, int i, long& blocks) -> int {
+        ADR_REQUIRE(en.src && en.dst && en.C > 0 && en.C % 8 == 0 && en.scs % 8 == 0 && en.dcs % 8 == 0 &&
+                        ((uintptr_t)en.src & 15) == 0 && ((uintptr_t)en.dst & 15) == 0 &&
+                        npix * (en.C / 8) < (1l << 31),
+                    "copy_pieces: piece %d (C=%d scs=%d dcs=%d)", i, en.C, en.scs, en.dcs);
+        blocks = cdiv(npix * (en.C / 8), 256);
+        return ADR_OK;
+      },
+      [&](CopyBatch& b, unsigned blocks) {
+        b.npix = (unsigned)npix;
+        hipLaunchKernelGGL(copy_pieces_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, b);
+      });
 }
 
 extern "C" int adr_axpy(long n, float a, const float* x, float* y, void* stream) {

@@ -472,18 +472,13 @@ __global__ void __launch_bounds__(256) wgrad_reduce_kernel(const float* __restri
 // (deterministic). The sum then lands at its (K, C, RS) parameter slot (or (C, K, RS) with transpose_kc).
 // Round 4: replaces a 32-output x 8-lane scalar version that read 4-byte words (l-scale: 800 us per launch).
 constexpr int RB_MAX = 56;
-struct RedBatch {
-  adr_wgrad_reduce_entry e[RB_MAX];  // e[j].pad_ carries the entry's split lanes (SL)
-  int start[RB_MAX + 1];
-  int count;
-};
+struct RedBatch : Batch<adr_wgrad_reduce_entry, RB_MAX> {};  // e[j].pad_ carries the entry's split lanes (SL)
 __global__ void __launch_bounds__(256) wgrad_reduce_batched_kernel(RedBatch b) {
-  int j = 0;
-  while (j + 1 < b.count && (int)blockIdx.x >= b.start[j + 1]) ++j;
-  const adr_wgrad_reduce_entry& en = b.e[j];
+  const BatchBlock bb = batch_block(b);
+  const adr_wgrad_reduce_entry& en = b.e[bb.j];
   const int SL = en.pad_, QPB = 256 / SL;
   const int q = threadIdx.x % QPB, lane = threadIdx.x / QPB;
-  const long i0 = ((long)(blockIdx.x - b.start[j]) * QPB + q) * 4;
+  const long i0 = ((long)(unsigned)bb.local * QPB + q) * 4;
   const long n = (long)en.K * en.RS * en.Cp;
   float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
   if (i0 < n) {
@@ -708,30 +703,23 @@ extern "C" int adr_wgrad_reduce_unpack(const float* part, long split_stride, int
 }
 
 extern "C" int adr_wgrad_reduce_batched(const adr_wgrad_reduce_entry* entries, int count, void* stream) {
-  ADR_REQUIRE(count >= 0 && (count == 0 || entries), "wgrad_reduce_batched: count=%d", count);
-  for (int b0 = 0; b0 < count; b0 += RB_MAX) {
-    RedBatch rb{};
-    rb.count = count - b0 < RB_MAX ? count - b0 : RB_MAX;
-    int blocks = 0;
-    for (int j = 0; j < rb.count; ++j) {
-      const adr_wgrad_reduce_entry& en = entries[b0 + j];
-      const long n = (long)en.K * en.RS * en.Cp;
-      ADR_REQUIRE(en.part && en.dst && n > 0 && en.splits >= 1 && en.C <= en.Cp && en.split_stride >= n &&
-                      en.Cp % 4 == 0 && en.split_stride % 4 == 0 && ((uintptr_t)en.part & 15) == 0,
-                  "wgrad_reduce_batched: entry %d (K=%d C=%d Cp=%d RS=%d splits=%d)", b0 + j, en.K, en.C, en.Cp,
-                  en.RS, en.splits);
-      for (int q = 0; q < j; ++q)  // same destination twice in one launch would race: the caller must split
-        ADR_REQUIRE(rb.e[q].dst != en.dst, "wgrad_reduce_batched: entries %d and %d share a destination", b0 + q,
-                    b0 + j);
-      rb.e[j] = en;
-      rb.e[j].pad_ = reduce_lanes(n, en.splits);
-      rb.start[j] = blocks;
-      blocks += (int)cdiv(n / 4, 256 / rb.e[j].pad_);
-    }
-    rb.start[rb.count] = blocks;
-    hipLaunchKernelGGL(wgrad_reduce_batched_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, rb);
-  }
-  return check_launch("adr_wgrad_reduce_batched");
+  return launch_batches<RedBatch>(
+      "adr_wgrad_reduce_batched", entries, count,
+      [](adr_wgrad_reduce_entry& en, int i, long& blocks) -> int {
+        const long n = (long)en.K * en.RS * en.Cp;
+        ADR_REQUIRE(en.part && en.dst && n > 0 && en.splits >= 1 && en.C <= en.Cp && en.split_stride >= n &&
+                        en.Cp % 4 == 0 && en.split_stride % 4 == 0 && ((uintptr_t)en.part & 15) == 0,
+                    "wgrad_reduce_batched: entry %d (K=%d C=%d Cp=%d RS=%d splits=%d)", i, en.K, en.C, en.Cp, en.RS,
+                    en.splits);
+        en.pad_ = reduce_lanes(n, en.splits);
+        blocks = cdiv(n / 4, 256 / en.pad_);
+        return ADR_OK;
+      },
+      [&](const RedBatch& b, unsigned blocks) {
+        hipLaunchKernelGGL(wgrad_reduce_batched_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, b);
+      },
+      // same destination twice in one launch would race: the caller must split
+      DupDst::Reject, [](const adr_wgrad_reduce_entry& a, const adr_wgrad_reduce_entry& en) { return a.dst == en.dst; });
 }
 
 extern "C" int adr_conv2d_wgrad(const adr_conv_desc* d, const void* x, const void* dy, float* dw, int accumulate,

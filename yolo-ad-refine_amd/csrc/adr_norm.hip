@@ -118,16 +118,11 @@ __global__ void __launch_bounds__(256) nc_reduce_kernel(const T* __restrict__ x,
 // to the end of backward): block b of the grid is (chunk, image) (b - start[e]) of entry e, reduced exactly as
 // nc_reduce_kernel reduces it, so the partial rows — and the bias gradients — are bitwise those of one launch each.
 constexpr int NCB_MAX = 48;
-struct NcrBatch {
-  adr_colsum_entry e[NCB_MAX];
-  int start[NCB_MAX + 1];
-  int count;
-};
+struct NcrBatch : Batch<adr_colsum_entry, NCB_MAX> {};
 __global__ void __launch_bounds__(256) nc_reduce_batched_kernel(NcrBatch b) {
-  int j = 0;
-  while (j + 1 < b.count && (int)blockIdx.x >= b.start[j + 1]) ++j;
-  const adr_colsum_entry& en = b.e[j];
-  const int local = blockIdx.x - b.start[j];
+  const BatchBlock bb = batch_block(b);
+  const adr_colsum_entry& en = b.e[bb.j];
+  const int local = bb.local;
   nc_reduce_body<__bf16, RED_STATS, ACT_NONE>((const __bf16*)en.x, en.xcs, 0, nullptr, 0, 0, nullptr, nullptr, 0,
                                               en.HW, en.C, en.rows_per_chunk, en.chunks, en.partial,
                                               local % en.chunks, local / en.chunks);
@@ -390,17 +385,12 @@ __global__ void __launch_bounds__(256) gn_bwd_param_kernel(const float* __restri
 // b - start[e] of entry e, reduced exactly as gn_bwd_param_kernel does. Entries of one launch have distinct
 // destinations (the host splits at a repeated one, so a shared module's contributions accumulate in order).
 constexpr int GPB_MAX = 40;
-struct GnParamBatch {
-  adr_gnparam_entry e[GPB_MAX];
-  int start[GPB_MAX + 1];
-  int count;
-};
+struct GnParamBatch : Batch<adr_gnparam_entry, GPB_MAX> {};
 __global__ void __launch_bounds__(256) gn_param_batched_kernel(GnParamBatch b) {
-  int j = 0;
-  while (j + 1 < b.count && (int)blockIdx.x >= b.start[j + 1]) ++j;
-  const adr_gnparam_entry& en = b.e[j];
+  const BatchBlock bb = batch_block(b);
+  const adr_gnparam_entry& en = b.e[bb.j];
   gn_bwd_param_body(en.partial, en.N, en.chunks, en.C, en.G, en.mean, en.rstd, en.dgamma, en.dbeta, en.accumulate,
-                    (int)blockIdx.x - b.start[j]);
+                    bb.local);
 }
 
 // ---- Level-packed GroupNorm (AYHead's three levels in one row space). The head stores a level's (image, H, W)
@@ -971,16 +961,11 @@ __global__ void __launch_bounds__(256) partial_sum_kernel(const float* __restric
 // Many partial sums per launch (the trainer defers the bias gradients to the end of backward): block j of the
 // grid reduces channel j - start[e] of entry e exactly as partial_sum_kernel does (same order).
 constexpr int PSB_MAX = 80;
-struct PsumBatch {
-  adr_psum_entry e[PSB_MAX];
-  int start[PSB_MAX + 1];
-  int count;
-};
+struct PsumBatch : Batch<adr_psum_entry, PSB_MAX> {};
 __global__ void __launch_bounds__(256) partial_sum_batched_kernel(PsumBatch b) {
-  int j = 0;
-  while (j + 1 < b.count && (int)blockIdx.x >= b.start[j + 1]) ++j;
-  const adr_psum_entry& en = b.e[j];
-  const int c = blockIdx.x - b.start[j];
+  const BatchBlock bb = batch_block(b);
+  const adr_psum_entry& en = b.e[bb.j];
+  const int c = bb.local;
   double a = 0.0, z = 0.0;
   for (int p = threadIdx.x; p < en.P; p += 256) a += en.partial[(long)p * 2 * en.C + en.which * en.C + c];
   block_sum2(a, z);
@@ -1189,47 +1174,33 @@ extern "C" int adr_affine_act_bwd(int dtype, const void* x, int xcs, int xco, co
 }
 
 extern "C" int adr_nc_reduce_batched(const adr_colsum_entry* entries, int count, void* stream) {
-  ADR_REQUIRE(count >= 0 && (count == 0 || entries), "nc_reduce_batched: count=%d", count);
-  for (int b0 = 0; b0 < count; b0 += NCB_MAX) {
-    NcrBatch nb{};
-    nb.count = count - b0 < NCB_MAX ? count - b0 : NCB_MAX;
-    long blocks = 0;
-    for (int j = 0; j < nb.count; ++j) {
-      const adr_colsum_entry& en = entries[b0 + j];
-      ADR_REQUIRE(en.x && en.partial && en.N > 0 && en.HW > 0 && en.C % 8 == 0 && en.C / 8 <= 256 &&
-                      en.xcs % 8 == 0 && ((uintptr_t)en.x & 15) == 0 && en.rows_per_chunk > 0 &&
-                      en.chunks == cdiv(en.HW, en.rows_per_chunk),
-                  "nc_reduce_batched: entry %d", b0 + j);
-      nb.e[j] = en;
-      nb.start[j] = (int)blocks;
-      blocks += (long)en.N * en.chunks;
-    }
-    ADR_REQUIRE(blocks < (1l << 31), "nc_reduce_batched: grid");
-    nb.start[nb.count] = (int)blocks;
-    hipLaunchKernelGGL(nc_reduce_batched_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, nb);
-  }
-  return check_launch("adr_nc_reduce_batched");
+  return launch_batches<NcrBatch>(
+      "adr_nc_reduce_batched", entries, count,
+      [](adr_colsum_entry& en, int i, long& blocks) -> int {
+        ADR_REQUIRE(en.x && en.partial && en.N > 0 && en.HW > 0 && en.C % 8 == 0 && en.C / 8 <= 256 &&
+                        en.xcs % 8 == 0 && ((uintptr_t)en.x & 15) == 0 && en.rows_per_chunk > 0 &&
+                        en.chunks == cdiv(en.HW, en.rows_per_chunk),
+                    "nc_reduce_batched: entry %d", i);
+        blocks = (long)en.N * en.chunks;
+        return ADR_OK;
+      },
+      [&](const NcrBatch& b, unsigned blocks) {
+        hipLaunchKernelGGL(nc_reduce_batched_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, b);
+      });
 }
 
 extern "C" int adr_partial_sum_batched(const adr_psum_entry* entries, int count, void* stream) {
-  ADR_REQUIRE(count >= 0 && (count == 0 || entries), "partial_sum_batched: count=%d", count);
-  for (int b0 = 0; b0 < count; b0 += PSB_MAX) {
-    PsumBatch pb{};
-    pb.count = count - b0 < PSB_MAX ? count - b0 : PSB_MAX;
-    int blocks = 0;
-    for (int j = 0; j < pb.count; ++j) {
-      const adr_psum_entry& en = entries[b0 + j];
-      ADR_REQUIRE(en.partial && en.out && en.P > 0 && en.C > 0, "partial_sum_batched: entry %d", b0 + j);
-      for (int q = 0; q < j; ++q)
-        ADR_REQUIRE(pb.e[q].out != en.out, "partial_sum_batched: entries %d and %d share a destination", b0 + q, b0 + j);
-      pb.e[j] = en;
-      pb.start[j] = blocks;
-      blocks += en.C;
-    }
-    pb.start[pb.count] = blocks;
-    hipLaunchKernelGGL(partial_sum_batched_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, pb);
-  }
-  return check_launch("adr_partial_sum_batched");
+  return launch_batches<PsumBatch>(
+      "adr_partial_sum_batched", entries, count,
+      [](adr_psum_entry& en, int i, long& blocks) -> int {
+        ADR_REQUIRE(en.partial && en.out && en.P > 0 && en.C > 0, "partial_sum_batched: entry %d", i);
+        blocks = en.C;
+        return ADR_OK;
+      },
+      [&](const PsumBatch& b, unsigned blocks) {
+        hipLaunchKernelGGL(partial_sum_batched_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, b);
+      },
+      DupDst::Reject, [](const adr_psum_entry& a, const adr_psum_entry& en) { return a.out == en.out; });
 }
 
 extern "C" int adr_partial_sum(const float* partial, int P, int C, int which, float* out, int accumulate,
@@ -1292,30 +1263,22 @@ extern "C" int adr_gn_act_bwd_fused(int dtype, const void* x, int xcs, int xco, 
 }
 
 extern "C" int adr_gn_param_grad_batched(const adr_gnparam_entry* entries, int count, void* stream) {
-  ADR_REQUIRE(count >= 0 && (count == 0 || entries), "gn_param_grad_batched: count=%d", count);
-  int b0 = 0;
-  while (b0 < count) {
-    GnParamBatch gb{};
-    int blocks = 0, j = 0;
-    for (; j < GPB_MAX && b0 + j < count; ++j) {
-      const adr_gnparam_entry& en = entries[b0 + j];
-      ADR_REQUIRE(en.partial && en.mean && en.rstd && (en.dgamma || en.dbeta) && en.N > 0 && en.chunks > 0 &&
-                      en.G > 0 && en.C % en.G == 0,
-                  "gn_param_grad_batched: entry %d", b0 + j);
-      bool dup = false;
-      for (int q = 0; q < j; ++q)
-        dup |= (en.dgamma && gb.e[q].dgamma == en.dgamma) || (en.dbeta && gb.e[q].dbeta == en.dbeta);
-      if (dup) break;  // a repeated destination starts the next launch (program-order accumulation)
-      gb.e[j] = en;
-      gb.start[j] = blocks;
-      blocks += en.C;
-    }
-    gb.count = j;
-    gb.start[j] = blocks;
-    hipLaunchKernelGGL(gn_param_batched_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, gb);
-    b0 += j;
-  }
-  return check_launch("adr_gn_param_grad_batched");
+  return launch_batches<GnParamBatch>(
+      "adr_gn_param_grad_batched", entries, count,
+      [](adr_gnparam_entry& en, int i, long& blocks) -> int {
+        ADR_REQUIRE(en.partial && en.mean && en.rstd && (en.dgamma || en.dbeta) && en.N > 0 && en.chunks > 0 &&
+                        en.G > 0 && en.C % en.G == 0,
+                    "gn_param_grad_batched: entry %d", i);
+        blocks = en.C;
+        return ADR_OK;
+      },
+      [&](const GnParamBatch& b, unsigned blocks) {
+        hipLaunchKernelGGL(gn_param_batched_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, b);
+      },
+      // a repeated destination starts the next launch (program-order accumulation)
+      DupDst::Split, [](const adr_gnparam_entry& a, const adr_gnparam_entry& en) {
+        return (en.dgamma && a.dgamma == en.dgamma) || (en.dbeta && a.dbeta == en.dbeta);
+      });
 }
 
 // host side of the level-packed statistics: k[l] sub-images per image of level l, `sub_rows` rows per sub-image

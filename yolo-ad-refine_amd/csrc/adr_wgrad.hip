@@ -321,19 +321,16 @@ __global__ void __launch_bounds__(256, DB ? 3 : 1) wgrad_bf16_kernel(WgArgs a) {
 // per-conv one. Small weight gradients (a 1x1 128 -> 128 at 20 x 20 is 100 workgroups for the whole chip) stop
 // costing a launch and a half-empty machine each.
 constexpr int WGB_MAX = 24;
-struct WgBatch {
-  WgArgs e[WGB_MAX];
-  int start[WGB_MAX + 1];
+struct WgBatch : Batch<WgArgs, WGB_MAX> {
   int tiles[WGB_MAX];
-  int count;
 };
 template <int BM, int BN, bool DB = false>
 __global__ void __launch_bounds__(256, DB ? 3 : 1) wgrad_bf16_batched_kernel(WgBatch b) {
-  int j = 0;
-  while (j + 1 < b.count && (int)blockIdx.x >= b.start[j + 1]) ++j;
+  const BatchBlock bb = batch_block(b);
+  const int j = bb.j;
   // XCD-aware order within the entry (every XCD gets an eighth of each entry, so the mix of long and short entries
   // stays balanced; the blocks of one entry with the same id % 8 share an XCD whatever start[j] is)
-  const int local = xcd_remap((int)blockIdx.x - b.start[j], b.start[j + 1] - b.start[j]);
+  const int local = xcd_remap(bb.local, b.start[j + 1] - b.start[j]);
   const int split = local / b.tiles[j];
   wgrad_bf16_body<BM, BN, wg_ku(BM, BN), DB>(b.e[j], local - split * b.tiles[j], split);
 }
