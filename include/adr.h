@@ -625,6 +625,15 @@ int adr_tta_view_size(void);
 int adr_tta_merge(const float* y0, const float* y1, const float* y2, const int* anchors, const int* keep0,
                   const int* keep1, const float* scales, const int* flips, float img_w, float* out, int B, int rows,
                   int A_total, void* stream);
+/* Multi-scale training's resample (models/yolo/detect/train.py:57-74 preprocess_batch with multi_scale): img
+ * (B, 3, H, W) uint8 NCHW -> out (B, 3, oh, ow) fp32 NCHW =
+ * F.interpolate(img.float() / 255, size=(oh, ow), mode="bilinear", align_corners=False), the fp32 image at the source
+ * size never written. v = (float)u8 * fp32(1/255) (as adr_stem_conv_fwd_u8 reads a uint8 batch), then ATen's fp32
+ * arithmetic, uncontracted, as adr_tta_views: scale = (float)in / out; src = max(scale * (dst + 0.5f) - 0.5f, 0);
+ * i0 = min((int)src, in - 1); i1 = min(i0 + 1, in - 1); l1 = src - i0; l0 = 1 - l1;
+ * l0y * (l0x * a + l1x * b) + l1y * (l0x * c + l1x * d). Any B, H, W, oh, ow >= 1; out 4-byte aligned (16-byte
+ * stores wherever a row's aligned groups of 4 lie inside it, single stores for its head and tail). */
+int adr_multiscale_u8(const uint8_t* img, int B, int H, int W, float* out, int oh, int ow, void* stream);
 /* W (Cout, C, 3, 3) fp32 -> [(tap*C + c)][Cout] operand for dcols = dy x W. */
 int adr_dcn_weight_t(int dtype, const float* w, void* out, int Cout, int C, void* stream);
 /* Per-image 2-layer gate MLP on pooled vectors: out = act2(W2 act1(W1 (in*in_scale) + b1) + b2);

@@ -27,6 +27,11 @@ with the collectives launched between replays. Per-step scalars (lr per group, m
 flag; for Adam the bias corrections of the step being taken) live in a device vector written by a stream-ordered
 kernel before each replay. Adam's beta1 is not warmed up (its param groups have no 'momentum', trainer.py:379).
 
+multi_scale=True (models/yolo/detect/train.py:57-74): every batch is resampled to multi_scale_shape's draw from the
+uint8 image in one launch (adr_multiscale_u8) and its targets are built at the new size. Captured steps are keyed by
+(image shape, dtype), then by target capacity; under multi_scale a drawn shape nobody captured runs eagerly, and
+capture(batch, size=(oh, ow)) captures one shape (at most `graph_shapes` shapes stay, least recently used evicted).
+
 Parameters that never receive a gradient (e.g. AdaptiveDynamicTanh.scale_weights, unused by the reference's
 forward) are skipped by SGD exactly like torch.optim.SGD skips p.grad is None.
 Mixed precision: the reference runs fp16 autocast + GradScaler; this build computes in bf16 (fp32 exponent
@@ -37,6 +42,8 @@ from __future__ import annotations
 import ctypes
 import math
 import os
+import random
+from collections import OrderedDict
 
 import numpy as np
 import torch
@@ -87,6 +94,18 @@ def resolve_optimizer(name, lr0, momentum, warmup_bias_lr, nc, iterations):
         f"Optimizer '{name}' not found in list of available optimizers "
         f"[Adam, AdamW, NAdam, RAdam, RMSProp, SGD, auto]."
         "To request support for addition optimizers please visit https://github.com/ultralytics/ultralytics.")
+
+
+def multi_scale_shape(imgsz, stride, hw, rng=random):
+    """The size multi_scale resamples a batch of (h, w) = `hw` images to (models/yolo/detect/train.py:60-71), or None
+    when the draw is 1:1 (the reference then skips the interpolate). One `randrange` per call, drawn whatever the
+    result, so a seeded `rng` walks the reference's sequence. `stride` is the trainer's max(int(model.stride.max()),
+    32) (engine/trainer.py:276-278)."""
+    sz = rng.randrange(int(imgsz * 0.5), int(imgsz * 1.5 + stride)) // stride * stride
+    sf = sz / max(hw)
+    if sf == 1:
+        return None
+    return [math.ceil(x * sf / stride) * stride for x in hw]
 
 
 def optimizer_iterations(n_images, batch_size, nbs, epochs):
@@ -163,13 +182,24 @@ class FusedTrainer:
     def __init__(self, model, lr0=0.01, momentum=0.937, weight_decay=5e-4, nbs=64, batch_size=64, world_size=1,
                  process_group=None, ema=True, ema_decay=0.9999, ema_tau=2000, max_norm=10.0, epochs=100, nb=None,
                  lrf=0.01, warmup_epochs=3.0, warmup_bias_lr=0.1, warmup_momentum=0.8, cos_lr=False, stages=None,
-                 collectives=None, optimizer="SGD", nc=None, iterations=None):
+                 collectives=None, optimizer="SGD", nc=None, iterations=None, multi_scale=False, imgsz=None,
+                 graph_shapes=4, rng=None):
         """optimizer: 'SGD' (default), 'Adam', 'AdamW' or 'auto' (resolve_optimizer; needs `iterations`, see
         optimizer_iterations). For Adam / AdamW `momentum` is beta1, as build_optimizer's betas=(momentum, 0.999).
         nc (used by 'auto' only) defaults to the detection head's nc: the reference's getattr(model, "nc", 10)
         reads the attribute its detection trainer attaches before build_optimizer runs (models/yolo/detect/train.py:81,
         model.nc = data["nc"]), and the head is built with that same class count — so the head's nc is what the
-        reference sees for a model that has one; the fallback 10 applies only to a model without a detection head."""
+        reference sees for a model that has one; the fallback 10 applies only to a model without a detection head.
+        multi_scale (needs `imgsz`, the reference's args.imgsz): every batch is resampled to multi_scale_shape's draw
+        by adr_multiscale_u8 from the dataloader's uint8 image, and its targets are built at the new size
+        (detect/train.py:57-74). `rng` (default: the `random` module, seeded per rank as the reference's) supplies the
+        draws. graph_shapes: how many image shapes keep captured graphs (least recently used evicted)."""
+        if multi_scale and imgsz is None:
+            raise ValueError("multi_scale=True needs `imgsz` (the size the draws are centred on)")
+        self.multi_scale = bool(multi_scale)
+        self.imgsz = imgsz
+        self.rng = random if rng is None else rng
+        self.graph_shapes = max(1, int(graph_shapes))
         if nc is None:
             nc = getattr(model, "nc", None) or getattr(getattr(model, "model", [None])[-1], "nc", 10)
         optimizer, lr0, momentum, warmup_bias_lr = resolve_optimizer(optimizer, lr0, momentum, warmup_bias_lr, nc,
@@ -178,6 +208,8 @@ class FusedTrainer:
         self.adam = optimizer != "SGD"
         self.beta2, self.eps = 0.999, 1e-8  # build_optimizer: betas=(momentum, 0.999), torch's default eps
         self.model = model
+        # the reference's self.stride (engine/trainer.py:276-278): the grid the drawn sizes are rounded to
+        self.ms_stride = max(int(model.stride.max()), 32) if self.multi_scale else None
         self.world_size = world_size
         # collectives=True issues the bucket all-reduces even at world_size 1 (a one-rank RCCL group exercises the
         # same interleaving of stage-graph replays and eager collectives as the multi-GPU step)
@@ -257,6 +289,10 @@ class FusedTrainer:
         self.hyper = torch.zeros(16, dtype=torch.float32, device=dev)
         self.graphs = None
         self._sets = {}  # target capacity -> (graphs, static batch): one captured step per capacity bucket
+        # captured steps are keyed by (image shape, dtype) first: `_sets` / `graphs` / `static_batch` are the ACTIVE
+        # shape's (`_key`); the other shapes' (sets, graphs, static batch) wait here, least recently used first
+        self._key = None
+        self._other = OrderedDict()
         self.packs = K.PackCache()
 
     def _build_table(self):
@@ -323,15 +359,31 @@ class FusedTrainer:
         lib.adr_opt_step(K.fptr(self.tab_dev), K.fptr(self.chunks_dev), self.nchunks, K.fptr(self.partial),
                          float(self.max_norm), K.fptr(self.hyper), K.fptr(self.norm), K.stream())
 
-    def _prepare(self, batch):
-        """{'img', 'gt'} on the device; 'gt' (B, nmax, 5) built from the collate_fn keys when absent."""
+    def _prepare(self, batch, size=None, draw=False):
+        """{'img', 'gt'} on the device; 'gt' (B, nmax, 5) built from the collate_fn keys when absent. With `draw`
+        (multi_scale steps) the image is resampled to multi_scale_shape's draw, with `size` to that (oh, ow); 'gt' is
+        then built from the normalised boxes at the NEW size — the loss works in pixels of the resized image, as the
+        reference's does through feats.shape * stride (utils/loss.py:216). A 1:1 draw leaves the uint8 image alone."""
         img = batch["img"]
         gt = batch.get("gt")
+        if gt is not None and (self.multi_scale or size is not None):
+            # pixel-space targets of the source size: rescaling them would round differently from the reference,
+            # which multiplies the normalised boxes by the new size once
+            raise ValueError("a batch with a prebuilt pixel-space 'gt' cannot be resampled (multi_scale / size=): "
+                             "pass the collate_fn keys batch_idx, cls, bboxes")
+        shape = None
+        if size is not None:
+            shape = [int(v) for v in size]
+        elif draw:
+            shape = multi_scale_shape(self.imgsz, self.ms_stride, img.shape[2:], self.rng)
+        img = img.to(self.dev, non_blocking=True)
+        if shape is not None and tuple(shape) != tuple(img.shape[2:]):
+            img = K.multi_scale_resize(img, shape)
         if gt is None:
             from ..utils.loss import preprocess_targets
             gt = preprocess_targets(batch["batch_idx"], batch["cls"], batch["bboxes"], img.shape[0],
                                     (img.shape[2], img.shape[3]))
-        return {"img": img.to(self.dev, non_blocking=True), "gt": gt.to(self.dev, non_blocking=True).float()}
+        return {"img": img, "gt": gt.to(self.dev, non_blocking=True).float()}
 
     def will_step(self):
         """Whether the next step() runs the optimizer (ni - last_opt_step >= accumulate, trainer.py:396)."""
@@ -347,9 +399,14 @@ class FusedTrainer:
         reduce_now = opt_now and self.collectives
         if opt_now:
             self._set_hyper()
-        if self.graphs is not None:
-            if batch is not self.static_batch:
-                b = self._prepare(batch)
+        b = self._prepare(batch, draw=True) if self.multi_scale else None
+        replay = self.graphs is not None
+        if replay and b is None and batch is not self.static_batch:
+            b = self._prepare(batch)
+        if replay and b is not None:
+            replay = self._select_shape(b)  # multi_scale: a drawn shape nobody captured runs eagerly
+        if replay:
+            if b is not None:
                 gt = b["gt"]
                 self._select_capacity(gt.shape[1], b)  # the smallest captured target capacity that holds the batch
                 self.static_batch["img"].copy_(b["img"], non_blocking=True)
@@ -366,7 +423,7 @@ class FusedTrainer:
             if opt_now:
                 g_opt.replay()
         else:
-            items = self.forward_backward(batch, self.reducer.launch if reduce_now else None)
+            items = self.forward_backward(batch if b is None else b, self.reducer.launch if reduce_now else None)
             if reduce_now:
                 self.reducer.wait()
             if self.tab_dev is None:  # the set of parameters that receive gradients is static: build once
@@ -387,6 +444,33 @@ class FusedTrainer:
         real dataloader (Poisson-like label counts, up to ~100 per image on COCO) needs a handful of captures."""
         return max(8, 1 << max(0, int(n) - 1).bit_length())
 
+    @staticmethod
+    def _shape_key(img):
+        return tuple(img.shape), img.dtype
+
+    def _activate(self, key):
+        """Make `key`'s captured sets the active ones; the active shape's wait in `_other` as most recently used."""
+        if self._key is not None and self._sets:
+            self._other[self._key] = (self._sets, self.graphs, self.static_batch)
+        self._sets, self.graphs, self.static_batch = self._other.pop(key, ({}, None, None))
+        self._key = key
+
+    def _select_shape(self, b):
+        """Activate the captured sets of b's (image shape, dtype); False when there are none and the step must run
+        eagerly. Without multi_scale an uncaptured shape is captured from this batch, as an uncaptured capacity is;
+        under multi_scale nothing is captured implicitly (21 shapes at imgsz 640, a whole step's activations each):
+        capture(batch, size=...) chooses the shapes that replay."""
+        key = self._shape_key(b["img"])
+        if key == self._key:
+            return True
+        if key in self._other:
+            self._activate(key)
+            return True
+        if self.multi_scale:
+            return False
+        self._capture(b)
+        return True
+
     def _select_capacity(self, need, b):
         """Activate the captured step with the smallest per-image target capacity >= need; capture one for
         capacity_bucket(need) (from this batch) when none holds it (capture() then drops the smaller sets). The
@@ -398,7 +482,7 @@ class FusedTrainer:
         if fits:
             self.graphs, self.static_batch = self._sets[min(fits)]
             return
-        self.capture(b, max_targets=self.capacity_bucket(need))
+        self._capture(b, max_targets=self.capacity_bucket(need))
 
     def _cap_floor(self):
         """Largest captured capacity below the active one (a batch above it keeps the active set)."""
@@ -406,13 +490,22 @@ class FusedTrainer:
         lower = [c for c in self._sets if c < cur]
         return max(lower) if lower else -1
 
-    def capture(self, batch, max_targets=None):
+    def capture(self, batch, max_targets=None, size=None):
         """Capture the step into HIP graphs. Call after at least one eager step (lazy caches, the parameter
         table). The batch becomes the graph's static input (targets padded to max_targets per image); later
-        `step(b)` copies b into it. The capture is kept keyed by its target capacity; the first batch that exceeds
-        it captures a larger bucket (capacity_bucket), which replaces every smaller one."""
+        `step(b)` copies b into it. The capture is kept keyed by its image shape and dtype, then by its target
+        capacity; the first batch of that shape that exceeds the capacity captures a larger bucket (capacity_bucket),
+        which replaces every smaller one of that shape. `size=(oh, ow)` captures the step at that multi-scale shape
+        (the uint8 batch resampled to it, no draw); at most `graph_shapes` shapes are kept, the least recently used
+        evicted."""
+        return self._capture(self._prepare(batch, size=size), max_targets)
+
+    def _capture(self, b, max_targets=None):
+        """capture() of a prepared batch {'img', 'gt'}."""
         assert self.tab_dev is not None, "run one eager step before capture()"
-        b = self._prepare(batch)
+        key = self._shape_key(b["img"])
+        if key != self._key:
+            self._activate(key)
         gt = b["gt"]
         cap = max(max_targets or gt.shape[1], gt.shape[1])
         sgt = torch.zeros(gt.shape[0], cap, 5, dtype=torch.float32, device=self.dev)
@@ -464,6 +557,9 @@ class FusedTrainer:
         self._sets[cap] = (self.graphs, self.static_batch)
         self.grad.copy_(gsaved)
         torch.cuda.synchronize()
+        while len(self._other) + 1 > self.graph_shapes:  # the least recently used shape's sets go, pools and all
+            self._other.popitem(last=False)
+            dropped = True
         if dropped:
             torch.cuda.empty_cache()  # return the dropped sets' private pools
         return self.static_batch

@@ -1713,6 +1713,24 @@ def image_to_nhwc(img: torch.Tensor, dtype, cpad=8):
     return out
 
 
+def multi_scale_resize(img_u8: torch.Tensor, size):
+    """Multi-scale training's resample (detect/train.py:57-74): (B, 3, H, W) uint8 -> (B, 3, oh, ow) fp32 =
+    F.interpolate(img.float() / 255, size=(oh, ow), mode="bilinear", align_corners=False) in one launch; the fp32
+    image at the source size is never written (adr_multiscale.hip)."""
+    _req_cuda(img_u8)
+    if img_u8.dtype != torch.uint8 or img_u8.dim() != 4 or img_u8.shape[1] != 3:
+        raise RuntimeError(f"adrefine: multi_scale_resize needs a (B, 3, H, W) uint8 batch, got "
+                           f"{tuple(img_u8.shape)} {img_u8.dtype}")
+    if not img_u8.is_contiguous():
+        relayout_count[0] += 1
+        img_u8 = img_u8.contiguous()
+    oh, ow = (int(v) for v in size)
+    B, _, H, W = img_u8.shape
+    out = torch.empty((B, 3, max(oh, 0), max(ow, 0)), dtype=torch.float32, device=img_u8.device)
+    lib.adr_multiscale_u8(fptr(img_u8), B, H, W, fptr(out), oh, ow, stream())
+    return out
+
+
 # ---------------------------------------------------------------------------------------------------------
 # functional entry points
 # ---------------------------------------------------------------------------------------------------------
