@@ -174,6 +174,11 @@ int adr_conv2d_wgrad_partials_batched(const adr_wgrad_job* jobs, int count, void
 /* The tile kernel a job of adr_conv2d_wgrad_partials_batched goes to: bm * 256 + bn of the grouped
  * wgrad_bf16_batched_kernel<bm, bn>, or 0 when the job runs its own thin / 3x3-halo kernel (bench timing labels). */
 int adr_conv2d_wgrad_batched_tile(const adr_conv_desc* d);
+/* Name of the kernel adr_conv2d_wgrad_partials[_bias] launches for this bf16 contraction, as rocprofv3 prints it,
+ * written to buf (len >= 64): wgrad3t_kernel<S, KB> (thin channels), wgrad3_kernel<TW, KF> (3x3 halo tiles) or
+ * wgrad_bf16_kernel<BM, BN[, true]> (generic tile; `true`: the double-buffered 128 x 128 one). Built from the
+ * launcher's own plan; launches nothing. */
+int adr_conv2d_wgrad_kernel_symbol(const adr_conv_desc* d, char* buf, int len);
 int adr_conv2d_wgrad_partials(const adr_conv_desc* d, const void* x, const void* dy, float* out, int accumulate,
                               void* stream);
 /* The bias gradient's column sums of dy computed by the weight-gradient GEMM that already holds dy in registers

@@ -1,4 +1,7 @@
-"""GPU parity: dense conv family (Conv-BN-SiLU, nn.Conv2d+bias, ConvTranspose2d) vs the CPU oracle."""
+"""GPU parity: dense conv family (Conv-BN-SiLU, nn.Conv2d+bias, ConvTranspose2d) vs the CPU oracle.
+
+These are module-level checks at the project's bf16 tolerances. Op-level coverage of the kernels behind them (every
+tile shape, split count and edge, bit-exact on integer inputs against float64) is in test_gpu_conv_exact.py."""
 import pytest
 import torch
 

@@ -495,6 +495,13 @@ def _conv2_symbol(d, dgrad):
     return buf.value.decode()
 
 
+def _wgrad_symbol(d):
+    """The bf16 weight-gradient kernel for this contraction, from the launcher's own plan (roofline label)."""
+    buf = ctypes.create_string_buffer(128)
+    lib.adr_conv2d_wgrad_kernel_symbol(ctypes.byref(d), buf, 128)
+    return buf.value.decode()
+
+
 def conv_fwd(d, xp, wp, bias, yp, stats=None, accumulate=0):
     """y (+)= conv(x, w_krsc) (+bias); optional per-128-row-tile BN partial statistics of the stored values."""
     e2 = _engine2(d, d.c)
@@ -966,8 +973,7 @@ def _wgrad_param(param, d, xp, dyp, K, C, RS, K_, C_, RS_, cpad, device, keep=()
     splits = lib.adr_conv2d_wgrad_splits(ctypes.byref(d))
     stride = K * RS * C
     es = 2 if d.dtype == BF16 else 4
-    name = (f"void adr::wgrad_bf16_kernel<{_bn_of(K)}, {_bn_of(C)}>(adr::WgArgs)" if d.dtype == BF16
-            else _gemm_symbol(F32, _bn_of(C), 2))
+    name = "" if _TIMING is None else _wgrad_symbol(d) if d.dtype == BF16 else _gemm_symbol(F32, _bn_of(C), 2)
     work = (es * (d.n * d.h * d.w * d.c + d.n * d.ho * d.wo * d.k) + 4 * stride, 2 * d.n * d.ho * d.wo * d.k * RS * d.c)
     shp = _shape(d, f"wgrad/{splits}") if _TIMING is not None else ""
     ws = torch.empty(splits * stride, dtype=torch.float32, device=device)
@@ -4058,8 +4064,7 @@ def wgrad_param_multi(param, pieces, K, C, RS, wshape, cpad, device, bias=None):
     s0 = 0
     for (d, xp, dyp), sp in zip(pieces, splits):
         es = 2 if d.dtype == BF16 else 4
-        name = (f"void adr::wgrad_bf16_kernel<{_bn_of(K)}, {_bn_of(C)}>(adr::WgArgs)" if d.dtype == BF16
-                else _gemm_symbol(F32, _bn_of(C), 2))
+        name = "" if _TIMING is None else _wgrad_symbol(d) if d.dtype == BF16 else _gemm_symbol(F32, _bn_of(C), 2)
         work = (es * (d.n * d.h * d.w * d.c + d.n * d.ho * d.wo * d.k) + 4 * sp * stride,
                 2 * d.n * d.ho * d.wo * d.k * RS * d.c)
         tok = _t0(name, *work, _shape(d, f"wgrad/{sp}") if _TIMING is not None else "")

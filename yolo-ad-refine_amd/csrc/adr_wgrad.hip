@@ -810,6 +810,22 @@ extern "C" int adr_conv2d_wgrad_batched_tile(const adr_conv_desc* d) {
   return (p.thin || p.tw3) ? 0 : p.bm * 256 + p.bn;
 }
 
+// The kernel a bf16 WGRAD's partials run on, from the plan the launcher itself follows (wgrad_bf16_launch), so the
+// roofline label and the tests' dispatch assertions cannot drift from the dispatch. Host only: launches nothing.
+extern "C" int adr_conv2d_wgrad_kernel_symbol(const adr_conv_desc* d, char* buf, int len) {
+  ADR_REQUIRE(d && buf && len >= 64 && d->dtype == ADR_BF16, "conv wgrad kernel symbol: bf16 descriptor and a buffer");
+  const WgPlan p = wgrad_bf16_plan(d);
+  if (p.thin)
+    snprintf(buf, len, "void adr::wgrad3t_kernel<%d, %d>(adr::WgArgs)", p.thin, p.bm);
+  else if (p.tw3)
+    snprintf(buf, len, "void adr::wgrad3_kernel<%d, %d>(adr::WgArgs)", p.tw3, p.bm / 16);
+  else if (p.bm == 128 && p.bn == 128 && wg_db())
+    snprintf(buf, len, "void adr::wgrad_bf16_kernel<128, 128, true>(adr::WgArgs)");
+  else
+    snprintf(buf, len, "void adr::wgrad_bf16_kernel<%d, %d>(adr::WgArgs)", p.bm, p.bn);
+  return ADR_OK;
+}
+
 extern "C" int adr_conv2d_wgrad_bias_fusable(const adr_conv_desc* d) {
   return d && d->dtype == ADR_BF16 && wgrad_bias_ok(wgrad_bf16_plan(d)) ? 1 : 0;
 }
