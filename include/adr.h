@@ -218,12 +218,20 @@ int adr_nc_reduce_chunks(int HW, int rows_per_chunk);
 int adr_nc_reduce(int dtype, int mode, const void* x, int xcs, int xco, const void* dz, int dcs, int dco,
                   const float* scale, const float* shift, int per_sample, int act, int N, int HW, int C,
                   int rows_per_chunk, float* partial, void* stream);
+/* BatchNorm finalize over [P][2][C] partial rows. A long finalize (many rows) first pre-sums blocks of rows into
+ * `scratch`, device memory the caller owns for the duration of the call on `stream`:
+ * adr_bn_finalize_scratch_floats(P, C) floats (0: the finalize is a single launch and needs none; the answer follows
+ * the ADR_FIN_PRESUM switch, read per call). The library cannot see the buffer's size, so a scratch shorter than the
+ * query's answer is written past its end. Its contents before and after the call are unspecified. scratch == NULL
+ * is always valid: a single-launch finalize at any P (the eval finalize, training = 0, never uses it). The library
+ * keeps no state between calls: concurrent finalizes on any streams are safe, each with a scratch of its own. */
+int adr_bn_finalize_scratch_floats(int P, int C);
 int adr_bn_finalize(const float* partial, int P, int C, double count, const float* gamma, const float* beta,
                     float* running_mean, float* running_var, float momentum, float eps, int training,
-                    float* scale, float* shift, float* mean, float* rstd, void* stream);
+                    float* scale, float* shift, float* mean, float* rstd, float* scratch, void* stream);
 int adr_bn_bwd_finalize(const float* partial, int P, int C, double count, const float* mean, const float* rstd,
                         const float* gamma, float* dgamma, float* dbeta, float* A, float* B, float* Cc,
-                        int training, int accumulate, void* stream);
+                        int training, int accumulate, float* scratch, void* stream);
 int adr_gn_finalize(const float* partial, int N, int chunks, int C, int G, double count, const float* gamma,
                     const float* beta, float eps, float* scale, float* shift, float* mean, float* rstd,
                     void* stream);

@@ -24,15 +24,17 @@ for C in (8, 16, 32, 64, 128, 256):
         res = []
         for kind, mode in (("fwd", "0"), ("fwd", "1"), ("bwd", "0"), ("bwd", "1")):
             os.environ["ADR_FIN_PRESUM"] = mode
+            nscr = lib.adr_bn_finalize_scratch_floats(P, C)  # 0: single launch (always in mode 0)
+            scr = torch.empty(nscr, device="cuda") if nscr else None
             def run():
                 st = K.stream()
                 for _ in range(50):
                     if kind == "fwd":
                         lib.adr_bn_finalize(fp(part), P, C, float(P * 128), fp(g), fp(b), fp(rm), fp(rv), 0.03, 1e-3, 1,
-                                            fp(sc), fp(sh), fp(mu), fp(rs), st)
+                                            fp(sc), fp(sh), fp(mu), fp(rs), fp(scr), st)
                     else:
                         lib.adr_bn_bwd_finalize(fp(part), P, C, float(P * 128), fp(mu), fp(rs), fp(g), fp(dg), fp(db),
-                                                fp(A), fp(B), fp(Cc), 1, 0, st)
+                                                fp(A), fp(B), fp(Cc), 1, 0, fp(scr), st)
             with torch.cuda.stream(s):
                 run()
             torch.cuda.synchronize()

@@ -37,6 +37,56 @@ def _stats_rows(N, HW):
     return rows
 
 
+# The norm passes over an NHWC view (pointer, channel stride) of N images of HW pixels (a packed activation: its Np
+# sub-images of S). The partials are allocated apart from the launches that fill them: a bias gradient or a
+# GroupNorm parameter gradient queues them for the deferral's flush in between.
+def _stat_part(N, HW, C, dev):
+    """(part, chunks): unwritten adr_nc_reduce partial rows [N * chunks][2][C] of an (N, HW, C) map."""
+    chunks = lib.adr_nc_reduce_chunks(HW, _stats_rows(N, HW))
+    return torch.empty(N * chunks * 2 * C, dtype=torch.float32, device=dev), chunks
+
+
+def _nc_stats(part, dt, xp, xcs, N, HW, C):
+    """The statistics pass (adr_nc_reduce mode 0): per-chunk (sum x, sum x^2) into part."""
+    lib.adr_nc_reduce(dt, 0, ctypes.c_void_p(xp), xcs, 0, None, 0, 0, None, None, 0, 0, N, HW, C, _stats_rows(N, HW),
+                      fptr(part), stream())
+
+
+def _nc_stats_bwd(part, dt, yp, ycs, dzp, dzcs, scale, shift, per_sample, act, N, HW, C):
+    """The backward statistics pass (mode 1): per-chunk (sum g, sum g * y), g = dz * act'(y * scale + shift)."""
+    lib.adr_nc_reduce(dt, 1, ctypes.c_void_p(yp), ycs, 0, ctypes.c_void_p(dzp), dzcs, 0, fptr(scale), fptr(shift),
+                      per_sample, ACT[act], N, HW, C, _stats_rows(N, HW), fptr(part), stream())
+
+
+def _affine_act(dt, yp, ycs, zp, zcs, scale, shift, per_sample, act, N, HW, C):
+    """z = act(y * scale + shift), coefficients per channel or per (image, channel)."""
+    lib.adr_affine_act(dt, ctypes.c_void_p(yp), ycs, 0, ctypes.c_void_p(zp), zcs, 0, fptr(scale), fptr(shift),
+                       per_sample, ACT[act], N, HW, C, stream())
+
+
+def _affine_act_bwd(dt, yp, ycs, dzp, dzcs, dyp, dycs, scale, shift, A, B, Cc, per_sample, act, N, HW, C):
+    """dy = A * g + B * y + C, g as in _nc_stats_bwd; coefficients per channel or per (image, channel)."""
+    lib.adr_affine_act_bwd(dt, ctypes.c_void_p(yp), ycs, 0, ctypes.c_void_p(dzp), dzcs, 0, ctypes.c_void_p(dyp), dycs,
+                           0, fptr(scale), fptr(shift), fptr(A), fptr(B), fptr(Cc), per_sample, per_sample, ACT[act],
+                           N, HW, C, 0, stream())
+
+
+def _gamma_beta_dst(gamma, beta, C, dev, norm):
+    """(dgamma, pg, dbeta, pb, accumulate): the grad_dst of a norm's two parameters, which one launch writes."""
+    dgamma, pg, acc_g = grad_dst(gamma, C, dev)
+    dbeta, pb, acc_b = grad_dst(beta, C, dev)
+    if acc_g != acc_b:
+        raise RuntimeError(f"{norm} gamma/beta gradients must share one destination kind")
+    return dgamma, pg, dbeta, pb, acc_g
+
+
+def _bn_fin_scratch(P, C, dev):
+    """The scratch a BN finalize of P partial rows pre-sums into (adr_bn_finalize_scratch_floats), None when the
+    finalize is a single launch. A small fp32 tensor from the caching allocator, like the partials."""
+    n = lib.adr_bn_finalize_scratch_floats(P, C)
+    return torch.empty(n, dtype=torch.float32, device=dev) if n else None
+
+
 # counts layout fix-ups (should stay 0 on the hot path; tests assert it)
 relayout_count = [0]
 
@@ -207,7 +257,8 @@ def _call_site():
     """The first caller outside this module's launch helpers (timing detail labels: which op issued a launch)."""
     import sys
     f = sys._getframe(2)
-    while f is not None and f.f_code.co_name in ("_ew", "_hook_call", "wrapper", "call", "__call__", "_call"):
+    while f is not None and f.f_code.co_name in ("_ew", "_hook_call", "wrapper", "call", "__call__", "_call",
+                                                 "_nc_stats", "_nc_stats_bwd", "_affine_act", "_affine_act_bwd"):
         f = f.f_back
     if f is None:
         return "?"
@@ -800,8 +851,7 @@ class WgradDeferral:
         N, C, H, W = dy.shape
         vx, vd = _v(x), _v(dy)
         rows = _stats_rows(N, H * W)
-        chunks = lib.adr_nc_reduce_chunks(H * W, rows)
-        part = torch.empty(N * chunks * 2 * C, dtype=torch.float32, device=dy.device)
+        part, chunks = _stat_part(N, H * W, C, dy.device)
         vd[0]._adr_pinned = True
         dy._adr_pinned = True
         self.dots.add(DotsumEntry(vx[1], vd[1], part.data_ptr(), out.data_ptr(), vx[2], vd[2], N, H * W, C, rows,
@@ -1024,8 +1074,7 @@ def _bias_grad(dy, K, N, HW, cs, param=None):
 
 def _bias_grad1(dy, K, N, HW, cs, param=None):
     dt = dcode(dy.dtype)
-    chunks = lib.adr_nc_reduce_chunks(HW, _stats_rows(N, HW))
-    part = torch.empty(N * chunks * 2 * K, dtype=torch.float32, device=dy.device)
+    part, chunks = _stat_part(N, HW, K, dy.device)
     if param is not None and _dfr() is not None and _TIMING is None and _DEFER_COLSUM and dt == BF16 and \
             dy.data_ptr() % 16 == 0 and cs % 8 == 0 and K % 8 == 0 and \
             _target(param) is not None:  # an arena destination: column sums and partial sums at the flush, batched
@@ -1033,8 +1082,7 @@ def _bias_grad1(dy, K, N, HW, cs, param=None):
         _dfr().add_colsum(dy, part, cs, N, HW, K, _stats_rows(N, HW), chunks)
         _dfr().add_psum(part, N * chunks, K, 0, p, acc)
         return grad_ret(param, db)
-    lib.adr_nc_reduce(dt, 0, ctypes.c_void_p(dy.data_ptr()), cs, 0, None, 0, 0, None, None, 0, 0, N, HW, K,
-                      _stats_rows(N, HW), fptr(part), stream())
+    _nc_stats(part, dt, dy.data_ptr(), cs, N, HW, K)
     if param is not None:
         db, p, acc = grad_dst(param, K, dy.device)
         if _dfr() is not None and acc and _TIMING is None:
@@ -1259,16 +1307,16 @@ class BNActFn(torch.autograd.Function):
         scale, shift, mean, rstd = f(), f(), f(), f()
         if training:
             if stats is None or stats.numel() == 0:
-                chunks = lib.adr_nc_reduce_chunks(HW, _stats_rows(N, HW))
-                stats = torch.empty(N * chunks * 2 * C, dtype=torch.float32, device=dev)
-                lib.adr_nc_reduce(dcode(dtype), 0, ctypes.c_void_p(yp), ycs, 0, None, 0, 0, None, None, 0, 0,
-                                  N, HW, C, _stats_rows(N, HW), fptr(stats), stream())
+                stats, _ = _stat_part(N, HW, C, dev)
+                _nc_stats(stats, dcode(dtype), yp, ycs, N, HW, C)
             P = stats.numel() // (2 * C)
         else:
             P = 0
+        scratch = _bn_fin_scratch(P, C, dev)  # None for eval (P = 0) and for a single-launch finalize
         lib.adr_bn_finalize(fptr(stats) if training else None, P, C, float(N * HW), fptr(gamma.detach()),
                             fptr(beta.detach()), fptr(rm), fptr(rv), float(momentum),
-                            float(eps), int(training), fptr(scale), fptr(shift), fptr(mean), fptr(rstd), stream())
+                            float(eps), int(training), fptr(scale), fptr(shift), fptr(mean), fptr(rstd), fptr(scratch),
+                            stream())
         z, zp, zcs = _out_view(box, N, C, H, W, dtype, dev)
         ctx.sres = getattr(res, "_adr_sink", None) if res is not None else None
         ctx.bstat = None
@@ -1284,8 +1332,7 @@ class BNActFn(torch.autograd.Function):
             ctx.bstat = BnStat(y, scale, shift, act) if BN_BSTAT else None
             BnFwd(y, scale, shift, act, z, ctx.bstat).attach()
         else:
-            lib.adr_affine_act(dcode(dtype), ctypes.c_void_p(yp), ycs, 0, ctypes.c_void_p(zp), zcs, 0,
-                               fptr(scale), fptr(shift), 0, ACT[act], N, HW, C, stream())
+            _affine_act(dcode(dtype), yp, ycs, zp, zcs, scale, shift, 0, act, N, HW, C)
         ctx.save_for_backward(y, scale, shift, mean, rstd, gamma)
         ctx.meta = (act, training)
         ctx.pbeta = beta
@@ -1306,23 +1353,19 @@ class BNActFn(torch.autograd.Function):
         HW = H * W
         dev = y.device
         dt = dcode(y.dtype)
-        chunks = lib.adr_nc_reduce_chunks(HW, _stats_rows(N, HW))
-        part = torch.empty(N * chunks * 2 * C, dtype=torch.float32, device=dev) if got is None else None
         f = lambda: torch.empty(C, dtype=torch.float32, device=dev)  # noqa: E731
         A, B, Cc = f(), f(), f()
-        dgamma, pg, acc_g = grad_dst(gamma, C, dev)
-        dbeta, pb, acc_b = grad_dst(ctx.pbeta, C, dev)
-        if acc_g != acc_b:
-            raise RuntimeError("BN gamma/beta gradients must share one destination kind")
+        dgamma, pg, dbeta, pb, acc_g = _gamma_beta_dst(gamma, ctx.pbeta, C, dev, "BN")
         if got is not None:
             part, P = got
         else:
+            part, chunks = _stat_part(N, HW, C, dev)
             P = N * chunks
-            lib.adr_nc_reduce(dt, 1, ctypes.c_void_p(yp), ycs, 0, ctypes.c_void_p(dzp), dzcs, 0, fptr(scale),
-                              fptr(shift), 0, ACT[act], N, HW, C, _stats_rows(N, HW), fptr(part), stream())
+            _nc_stats_bwd(part, dt, yp, ycs, dzp, dzcs, scale, shift, 0, act, N, HW, C)
+        scratch = _bn_fin_scratch(P, C, dev)
         lib.adr_bn_bwd_finalize(fptr(part), P, C, float(N * HW), fptr(mean), fptr(rstd),
                                 fptr(gamma.detach()), pg, pb, fptr(A), fptr(B), fptr(Cc), int(training), acc_g,
-                                stream())
+                                fptr(scratch), stream())
         dy = empty_act(N, C, H, W, y.dtype, dev)
         pend = BnXf(y, dz, scale, shift, A, B, Cc, act)
         if ctx.xfuse:  # the conv's data gradient applies it while staging its operand (and side-writes dy)
@@ -1380,8 +1423,7 @@ class BnFwd:
         y, yp, ycs = nhwc(self.y)
         z, zp, zcs = nhwc(self.z)
         N, C, H, W = y.shape
-        lib.adr_affine_act(dcode(y.dtype), ctypes.c_void_p(yp), ycs, 0, ctypes.c_void_p(zp), zcs, 0, fptr(self.scale),
-                           fptr(self.shift), 0, ACT[self.act], N, H * W, C, stream())
+        _affine_act(dcode(y.dtype), yp, ycs, zp, zcs, self.scale, self.shift, 0, self.act, N, H * W, C)
 
     def struct(self):
         _, yp, ycs = nhwc(self.y)
@@ -1511,10 +1553,8 @@ class BnXf:
         y, yp, ycs = nhwc(self.y)
         _, dzp, dzcs = nhwc(self.dz)
         N, C, H, W = y.shape
-        lib.adr_affine_act_bwd(dcode(y.dtype), ctypes.c_void_p(yp), ycs, 0, ctypes.c_void_p(dzp), dzcs, 0,
-                               ctypes.c_void_p(dy.data_ptr()), dy.stride(3), 0, fptr(self.scale), fptr(self.shift),
-                               fptr(self.A), fptr(self.B), fptr(self.Cc), 0, 0, ACT[self.act], N, H * W, C, 0,
-                               stream())
+        _affine_act_bwd(dcode(y.dtype), yp, ycs, dzp, dzcs, dy.data_ptr(), dy.stride(3), self.scale, self.shift,
+                        self.A, self.B, self.Cc, 0, self.act, N, H * W, C)
 
     def struct(self, dy):
         _, yp, ycs = nhwc(self.y)
@@ -1565,33 +1605,23 @@ class GNActFn(torch.autograd.Function):
         HW = H * W
         dev = y.device
         ctx.fused = _GN_FUSED and HW <= _GN_FUSED_MAXHW and bool(lib.adr_gn_fused_supported(dcode(dtype), C, groups))
-        if ctx.fused:  # one launch per layer: a workgroup per image does statistics + affine + activation
-            scale = torch.empty(N * C, dtype=torch.float32, device=dev)
-            shift = torch.empty(N * C, dtype=torch.float32, device=dev)
-            mean = torch.empty(N * groups, dtype=torch.float32, device=dev)
-            rstd = torch.empty(N * groups, dtype=torch.float32, device=dev)
-            z = empty_act(N, C, H, W, dtype, dev)
-            lib.adr_gn_act_fused(dcode(dtype), ctypes.c_void_p(yp), ycs, 0, ctypes.c_void_p(z.data_ptr()), C, 0,
-                                 fptr(gamma.detach()), fptr(beta.detach()), float(eps), N, HW, C, groups, ACT[act],
-                                 fptr(scale), fptr(shift), fptr(mean), fptr(rstd), stream())
-            ctx.save_for_backward(y, scale, shift, mean, rstd, gamma)
-            ctx.meta = (groups, act)
-            ctx.pbeta = beta
-            return z
-        chunks = lib.adr_nc_reduce_chunks(HW, _stats_rows(N, HW))
-        part = torch.empty(N * chunks * 2 * C, dtype=torch.float32, device=dev)
         scale = torch.empty(N * C, dtype=torch.float32, device=dev)
         shift = torch.empty(N * C, dtype=torch.float32, device=dev)
         mean = torch.empty(N * groups, dtype=torch.float32, device=dev)
         rstd = torch.empty(N * groups, dtype=torch.float32, device=dev)
-        lib.adr_nc_reduce(dcode(dtype), 0, ctypes.c_void_p(yp), ycs, 0, None, 0, 0, None, None, 0, 0, N, HW, C,
-                          _stats_rows(N, HW), fptr(part), stream())
-        lib.adr_gn_finalize(fptr(part), N, chunks, C, groups, float(HW * (C // groups)), fptr(gamma.detach()),
-                            fptr(beta.detach()), float(eps), fptr(scale), fptr(shift), fptr(mean), fptr(rstd),
-                            stream())
-        z = empty_act(N, C, H, W, dtype, dev)
-        lib.adr_affine_act(dcode(dtype), ctypes.c_void_p(yp), ycs, 0, ctypes.c_void_p(z.data_ptr()), C, 0,
-                           fptr(scale), fptr(shift), 1, ACT[act], N, HW, C, stream())
+        if ctx.fused:  # one launch per layer: a workgroup per image does statistics + affine + activation
+            z = empty_act(N, C, H, W, dtype, dev)
+            lib.adr_gn_act_fused(dcode(dtype), ctypes.c_void_p(yp), ycs, 0, ctypes.c_void_p(z.data_ptr()), C, 0,
+                                 fptr(gamma.detach()), fptr(beta.detach()), float(eps), N, HW, C, groups, ACT[act],
+                                 fptr(scale), fptr(shift), fptr(mean), fptr(rstd), stream())
+        else:
+            part, chunks = _stat_part(N, HW, C, dev)
+            _nc_stats(part, dcode(dtype), yp, ycs, N, HW, C)
+            lib.adr_gn_finalize(fptr(part), N, chunks, C, groups, float(HW * (C // groups)), fptr(gamma.detach()),
+                                fptr(beta.detach()), float(eps), fptr(scale), fptr(shift), fptr(mean), fptr(rstd),
+                                stream())
+            z = empty_act(N, C, H, W, dtype, dev)
+            _affine_act(dcode(dtype), yp, ycs, z.data_ptr(), C, scale, shift, 1, act, N, HW, C)
         ctx.save_for_backward(y, scale, shift, mean, rstd, gamma)
         ctx.meta = (groups, act)
         ctx.pbeta = beta
@@ -1614,10 +1644,7 @@ class GNActFn(torch.autograd.Function):
                                      ctypes.c_void_p(dy.data_ptr()), C, 0, fptr(scale), fptr(shift), fptr(mean),
                                      fptr(rstd), fptr(gamma.detach()), N, HW, C, groups, ACT[act], fptr(part),
                                      stream())
-            dgamma, pg, acc_g = grad_dst(gamma, C, dev)
-            dbeta, pb, acc_b = grad_dst(ctx.pbeta, C, dev)
-            if acc_g != acc_b:
-                raise RuntimeError("GN gamma/beta gradients must share one destination kind")
+            dgamma, pg, dbeta, pb, acc_g = _gamma_beta_dst(gamma, ctx.pbeta, C, dev, "GN")
             if _defer_gn(acc_g):
                 _dfr().add_gnparam(part, mean, rstd, pg, pb, N, 1, C, groups, acc_g)
             else:
@@ -1625,27 +1652,20 @@ class GNActFn(torch.autograd.Function):
             if ctx.gate is not None:
                 _gn_gate_grad(ctx.gate, ctx.eps, part, [1], N, 1, HW, C, groups, [gamma.detach()], mean, rstd, dy)
             return dy, grad_ret(gamma, dgamma), grad_ret(ctx.pbeta, dbeta), None, None, None
-        chunks = lib.adr_nc_reduce_chunks(HW, _stats_rows(N, HW))
-        part = torch.empty(N * chunks * 2 * C, dtype=torch.float32, device=dev)
-        dgamma, pg, acc_g = grad_dst(gamma, C, dev)
-        dbeta, pb, acc_b = grad_dst(ctx.pbeta, C, dev)
-        if acc_g != acc_b:
-            raise RuntimeError("GN gamma/beta gradients must share one destination kind")
+        part, chunks = _stat_part(N, HW, C, dev)
+        dgamma, pg, dbeta, pb, acc_g = _gamma_beta_dst(gamma, ctx.pbeta, C, dev, "GN")
         A = torch.empty(N * C, dtype=torch.float32, device=dev)
         B = torch.empty(N * C, dtype=torch.float32, device=dev)
         Cc = torch.empty(N * C, dtype=torch.float32, device=dev)
         dfr = _defer_gn(acc_g)  # dgamma / dbeta at the flush, batched (the coefficients are needed now)
         if dfr:
             _dfr().add_gnparam(part, mean, rstd, pg, pb, N, chunks, C, groups, acc_g)
-        lib.adr_nc_reduce(dt, 1, ctypes.c_void_p(yp), ycs, 0, ctypes.c_void_p(dzp), dzcs, 0, fptr(scale),
-                          fptr(shift), 1, ACT[act], N, HW, C, _stats_rows(N, HW), fptr(part), stream())
+        _nc_stats_bwd(part, dt, yp, ycs, dzp, dzcs, scale, shift, 1, act, N, HW, C)
         lib.adr_gn_bwd_finalize(fptr(part), N, chunks, C, groups, float(HW * (C // groups)), fptr(mean),
                                 fptr(rstd), fptr(gamma.detach()), None if dfr else pg, None if dfr else pb,
                                 fptr(A), fptr(B), fptr(Cc), acc_g, stream())
         dy = empty_act(N, C, H, W, y.dtype, dev)
-        lib.adr_affine_act_bwd(dt, ctypes.c_void_p(yp), ycs, 0, ctypes.c_void_p(dzp), dzcs, 0,
-                               ctypes.c_void_p(dy.data_ptr()), C, 0, fptr(scale), fptr(shift), fptr(A), fptr(B),
-                               fptr(Cc), 1, 1, ACT[act], N, HW, C, 0, stream())
+        _affine_act_bwd(dt, yp, ycs, dzp, dzcs, dy.data_ptr(), C, scale, shift, A, B, Cc, 1, act, N, HW, C)
         if ctx.gate is not None:
             _gn_gate_grad(ctx.gate, ctx.eps, part, [1], N, chunks, HW, C, groups, [gamma.detach()], mean, rstd, dy)
         return dy, grad_ret(gamma, dgamma), grad_ret(ctx.pbeta, dbeta), None, None, None
@@ -1824,7 +1844,7 @@ def _bn_eval_coefs_into(bn, scale, shift):
     C = scale.numel()
     lib.adr_bn_finalize(None, 0, C, 1.0, fptr(bn.weight.detach()), fptr(bn.bias.detach()), fptr(bn.running_mean),
                         fptr(bn.running_var), float(bn.momentum), float(bn.eps), 0, fptr(scale), fptr(shift), None,
-                        None, stream())
+                        None, None, stream())
 
 
 def _bn_eval_coefs(bn, dev):
@@ -2338,8 +2358,7 @@ def _reduce_dot(x, dy, sum_n, sum_c, which=0):
     N, C, H, W = dy.shape
     vd = _v(dy)
     vx = _v(x) if x is not None else (None, 0, 0)
-    chunks = lib.adr_nc_reduce_chunks(H * W, _stats_rows(N, H * W))
-    part = torch.empty(N * chunks * 2 * C, dtype=torch.float32, device=dy.device)
+    part, chunks = _stat_part(N, H * W, C, dy.device)
     lib.adr_dot_reduce(dcode(dy.dtype), ctypes.c_void_p(vx[1]) if x is not None else None, vx[2],
                        ctypes.c_void_p(vd[1]), vd[2], N, H * W, C, _stats_rows(N, H * W), fptr(part), stream())
     out = torch.empty((1 if sum_n else N) * (1 if sum_c else C), dtype=torch.float32, device=dy.device)
@@ -3911,31 +3930,27 @@ class GNPackFn(torch.autograd.Function):
         nl = len(params) // 2
         gam = [params[l if per_level else 0].detach() for l in range(pack.L)]
         bet = [params[nl + (l if per_level else 0)].detach() for l in range(pack.L)]
-        rows = _stats_rows(Np, S)
-        chunks = lib.adr_nc_reduce_chunks(S, rows)
-        part = torch.empty(Np * chunks * 2 * C, dtype=torch.float32, device=dev)
+        part, chunks = _stat_part(Np, S, C, dev)
         scale = torch.empty(Np * C, dtype=torch.float32, device=dev)
         shift = torch.empty(Np * C, dtype=torch.float32, device=dev)
         mean = torch.empty(Np * groups, dtype=torch.float32, device=dev)
         rstd = torch.empty(Np * groups, dtype=torch.float32, device=dev)
-        lib.adr_nc_reduce(dcode(dtype), 0, ctypes.c_void_p(yp), ycs, 0, None, 0, 0, None, None, 0, 0, Np, S, C, rows,
-                          fptr(part), stream())
+        _nc_stats(part, dcode(dtype), yp, ycs, Np, S, C)
         (gp, _ga), (bp, _ba) = _ptrs(gam), _ptrs(bet)
         lib.adr_gn_finalize_packed(fptr(part), pack.L, ctypes.cast(pack.k_c, ctypes.c_void_p), pack.N, chunks, S, C,
                                    groups, gp, bp, float(eps), fptr(scale), fptr(shift), fptr(mean), fptr(rstd),
                                    stream())
         z = pack.empty(C, dtype, dev)
-        lib.adr_affine_act(dcode(dtype), ctypes.c_void_p(yp), ycs, 0, ctypes.c_void_p(z.data_ptr()), C, 0,
-                           fptr(scale), fptr(shift), 1, ACT[act], Np, S, C, stream())
+        _affine_act(dcode(dtype), yp, ycs, z.data_ptr(), C, scale, shift, 1, act, Np, S, C)
         ctx.save_for_backward(y, scale, shift, mean, rstd)
-        ctx.meta = (groups, act, bool(per_level), chunks, rows)
+        ctx.meta = (groups, act, bool(per_level))
         ctx.pack, ctx.params = pack, params
         return z
 
     @staticmethod
     def backward(ctx, dz):
         y, scale, shift, mean, rstd = ctx.saved_tensors
-        groups, act, per_level, chunks, rows = ctx.meta
+        groups, act, per_level = ctx.meta
         pack, params = ctx.pack, ctx.params
         dz, dzp, dzcs = nhwc(dz.to(y.dtype) if dz.dtype != y.dtype else dz)
         _, yp, ycs = nhwc(y)
@@ -3943,9 +3958,8 @@ class GNPackFn(torch.autograd.Function):
         dev = y.device
         dt = dcode(y.dtype)
         nl = len(params) // 2
-        part = torch.empty(Np * chunks * 2 * C, dtype=torch.float32, device=dev)
-        lib.adr_nc_reduce(dt, 1, ctypes.c_void_p(yp), ycs, 0, ctypes.c_void_p(dzp), dzcs, 0, fptr(scale),
-                          fptr(shift), 1, ACT[act], Np, S, C, rows, fptr(part), stream())
+        part, chunks = _stat_part(Np, S, C, dev)
+        _nc_stats_bwd(part, dt, yp, ycs, dzp, dzcs, scale, shift, 1, act, Np, S, C)
         A = torch.empty(Np * C, dtype=torch.float32, device=dev)
         B = torch.empty(Np * C, dtype=torch.float32, device=dev)
         Cc = torch.empty(Np * C, dtype=torch.float32, device=dev)
@@ -3953,9 +3967,7 @@ class GNPackFn(torch.autograd.Function):
         lib.adr_gn_bwd_coef_packed(fptr(part), pack.L, ctypes.cast(pack.k_c, ctypes.c_void_p), pack.N, chunks, S, C,
                                    groups, gp, fptr(mean), fptr(rstd), fptr(A), fptr(B), fptr(Cc), stream())
         dy = pack.empty(C, y.dtype, dev)
-        lib.adr_affine_act_bwd(dt, ctypes.c_void_p(yp), ycs, 0, ctypes.c_void_p(dzp), dzcs, 0,
-                               ctypes.c_void_p(dy.data_ptr()), C, 0, fptr(scale), fptr(shift), fptr(A), fptr(B),
-                               fptr(Cc), 1, 1, ACT[act], Np, S, C, 0, stream())
+        _affine_act_bwd(dt, yp, ycs, dzp, dzcs, dy.data_ptr(), C, scale, shift, A, B, Cc, 1, act, Np, S, C)
         if ctx.gate is not None:
             _gn_gate_grad(ctx.gate, ctx.eps, part, list(pack.k), pack.N, chunks, S, C, groups,
                           [params[l if per_level else 0].detach() for l in range(pack.L)], mean, rstd, dy)
@@ -3964,10 +3976,7 @@ class GNPackFn(torch.autograd.Function):
             s0, n = (pack.sub0[j], pack.N * pack.k[j]) if per_level else (0, Np)
             pv, mv, rv = part[s0 * chunks * 2 * C:], mean[s0 * groups:], rstd[s0 * groups:]
             gam, bet = params[j], params[nl + j]
-            dgamma, pg, acc_g = grad_dst(gam, C, dev)
-            dbeta, pb, acc_b = grad_dst(bet, C, dev)
-            if acc_g != acc_b:
-                raise RuntimeError("GN gamma/beta gradients must share one destination kind")
+            dgamma, pg, dbeta, pb, acc_g = _gamma_beta_dst(gam, bet, C, dev, "GN")
             if _defer_gn(acc_g):
                 _dfr().add_gnparam(pv, mv, rv, pg, pb, n, chunks, C, groups, acc_g)
             else:
@@ -4447,52 +4456,42 @@ class BNPackFn(torch.autograd.Function):
         y, yp, ycs = nhwc(y)
         Np, C, _, S = y.shape
         dev = y.device
-        rows = _stats_rows(Np, S)
-        chunks = lib.adr_nc_reduce_chunks(S, rows)
-        part = torch.empty(Np * chunks * 2 * C, dtype=torch.float32, device=dev)
+        part, chunks = _stat_part(Np, S, C, dev)
         scale = torch.empty(Np * C, dtype=torch.float32, device=dev)
         shift = torch.empty(Np * C, dtype=torch.float32, device=dev)
         mean = torch.empty(pack.L * C, dtype=torch.float32, device=dev)
         rstd = torch.empty(pack.L * C, dtype=torch.float32, device=dev)
-        lib.adr_nc_reduce(dcode(dtype), 0, ctypes.c_void_p(yp), ycs, 0, None, 0, 0, None, None, 0, 0, Np, S, C, rows,
-                          fptr(part), stream())
+        _nc_stats(part, dcode(dtype), yp, ycs, Np, S, C)
         lib.adr_bn_finalize_packed(fptr(part), pack.L, ctypes.cast(pack.k_c, ctypes.c_void_p), pack.N, chunks, S, C,
                                    fptr(gamma.detach()), fptr(beta.detach()), fptr(rm), fptr(rv), float(momentum),
                                    float(eps), fptr(scale), fptr(shift), fptr(mean), fptr(rstd), stream())
         z = pack.empty(C, dtype, dev)
-        lib.adr_affine_act(dcode(dtype), ctypes.c_void_p(yp), ycs, 0, ctypes.c_void_p(z.data_ptr()), C, 0,
-                           fptr(scale), fptr(shift), 1, ACT[act], Np, S, C, stream())
+        _affine_act(dcode(dtype), yp, ycs, z.data_ptr(), C, scale, shift, 1, act, Np, S, C)
         ctx.save_for_backward(y, scale, shift, mean, rstd, gamma)
-        ctx.meta = (act, chunks, rows)
+        ctx.meta = act
         ctx.pack, ctx.pbeta = pack, beta
         return z
 
     @staticmethod
     def backward(ctx, dz):
         y, scale, shift, mean, rstd, gamma = ctx.saved_tensors
-        act, chunks, rows = ctx.meta
+        act = ctx.meta
         pack = ctx.pack
         dz, dzp, dzcs = nhwc(dz.to(y.dtype) if dz.dtype != y.dtype else dz)
         _, yp, ycs = nhwc(y)
         Np, C, _, S = y.shape
         dev = y.device
         dt = dcode(y.dtype)
-        part = torch.empty(Np * chunks * 2 * C, dtype=torch.float32, device=dev)
-        lib.adr_nc_reduce(dt, 1, ctypes.c_void_p(yp), ycs, 0, ctypes.c_void_p(dzp), dzcs, 0, fptr(scale),
-                          fptr(shift), 1, ACT[act], Np, S, C, rows, fptr(part), stream())
+        part, chunks = _stat_part(Np, S, C, dev)
+        _nc_stats_bwd(part, dt, yp, ycs, dzp, dzcs, scale, shift, 1, act, Np, S, C)
         f = lambda: torch.empty(Np * C, dtype=torch.float32, device=dev)  # noqa: E731
         A, B, Cc = f(), f(), f()
-        dgamma, pg, acc_g = grad_dst(gamma, C, dev)
-        dbeta, pb, acc_b = grad_dst(ctx.pbeta, C, dev)
-        if acc_g != acc_b:
-            raise RuntimeError("BN gamma/beta gradients must share one destination kind")
+        dgamma, pg, dbeta, pb, acc_g = _gamma_beta_dst(gamma, ctx.pbeta, C, dev, "BN")
         lib.adr_bn_bwd_finalize_packed(fptr(part), pack.L, ctypes.cast(pack.k_c, ctypes.c_void_p), pack.N, chunks, S,
                                        C, fptr(mean), fptr(rstd), fptr(gamma.detach()), pg, pb, fptr(A), fptr(B),
                                        fptr(Cc), acc_g, stream())
         dy = pack.empty(C, y.dtype, dev)
-        lib.adr_affine_act_bwd(dt, ctypes.c_void_p(yp), ycs, 0, ctypes.c_void_p(dzp), dzcs, 0,
-                               ctypes.c_void_p(dy.data_ptr()), C, 0, fptr(scale), fptr(shift), fptr(A), fptr(B),
-                               fptr(Cc), 1, 1, ACT[act], Np, S, C, 0, stream())
+        _affine_act_bwd(dt, yp, ycs, dzp, dzcs, dy.data_ptr(), C, scale, shift, A, B, Cc, 1, act, Np, S, C)
         return dy, None, grad_ret(gamma, dgamma), grad_ret(ctx.pbeta, dbeta), None, None, None, None, None
 
 

@@ -136,7 +136,8 @@ _NONSTATUS = {"adr_abi_version", "adr_conv2d_wgrad_bias_fusable", "adr_dwconv_wg
               "adr_dwconv_fwd_act_supported", "adr_dwconv_bwd_fused_supported", "adr_conv2d_bf16_xf_reuse", "adr_augment_desc_size",
               "adr_letterbox_desc_size", "adr_resize_desc_size", "adr_augment_mix_desc_size",
               "adr_dcn_bwd_tiles", "adr_conv2d_fwd_bf16_bnact_stat_tiles",
-              "adr_conv2d_dgrad_bf16_stat_tiles", "adr_conv2d_wgrad_batched_tile", "adr_tta_view_size"}
+              "adr_conv2d_dgrad_bf16_stat_tiles", "adr_conv2d_wgrad_batched_tile", "adr_tta_view_size",
+              "adr_bn_finalize_scratch_floats"}
 _ = _NONSTATUS
 
 lib = _Lib()

@@ -168,18 +168,16 @@ __device__ __forceinline__ void col_sums2(const float* __restrict__ partial, int
   b = (b + b1) + (b2 + b3);
 }
 
-// pre-summed partial rows of a long finalize (fin_presum_kernel, below)
-constexpr int FIN_PMAX = 2048, FIN_S = 256, FIN_SCRATCH = 1 << 20;  // floats
-__device__ float g_fin_scratch[FIN_SCRATCH];
+// long finalizes pre-sum their partial rows into at most FIN_S rows of caller scratch (fin_presum_kernel, below)
+constexpr int FIN_PMAX = 2048, FIN_S = 256;
 
 __global__ void __launch_bounds__(256) bn_finalize_kernel(const float* __restrict__ partial, int P, int C, double count,
                                                           const float* __restrict__ gamma,
                                                           const float* __restrict__ beta, float* running_mean,
                                                           float* running_var, float momentum, float eps,
                                                           int training, float* scale, float* shift, float* mean_out,
-                                                          float* rstd_out, int presummed) {
+                                                          float* rstd_out) {
   int c = blockIdx.x;
-  if (presummed) partial = g_fin_scratch;
   double mean, var;
   if (training) {
     double a = 0.0, b = 0.0;
@@ -213,9 +211,8 @@ __global__ void __launch_bounds__(256) bn_bwd_finalize_kernel(const float* __res
                                                               const float* __restrict__ rstd,
                                                               const float* __restrict__ gamma, float* dgamma,
                                                               float* dbeta, float* A, float* B, float* Cc,
-                                                              int training, int accumulate, int presummed) {
+                                                              int training, int accumulate) {
   int c = blockIdx.x;
-  if (presummed) partial = g_fin_scratch;
   double a = 0.0, b = 0.0;
   col_sums2(partial, P, C, c, a, b);
   block_sum2(a, b);
@@ -1031,12 +1028,13 @@ static bool fin_presum_off() {
 // launches: the per-channel kernels above read one 4-byte column per block, so a block's P row reads are P separate
 // cache lines and every channel block walks the same lines (14 us at P = 12 800, C = 32; 45 us at C = 256, against
 // 3 us for P = 50). fin_presum_kernel first sums blocks of `rb` consecutive rows of all 2C columns with coalesced
-// reads over the whole chip (double accumulation, fixed order) into the device-global scratch, and the finalize
-// reduces those <= FIN_S rows. Deterministic (the split depends on P only); the finalizes of a process are issued
-// on one stream (the scratch is not per-stream).
+// reads over the whole chip (double accumulation, fixed order) into `out`, the caller's scratch of
+// adr_bn_finalize_scratch_floats(P, C) floats, and the finalize reduces those <= FIN_S rows from there.
+// Deterministic (the split depends on P only). The scratch belongs to the call, so finalizes on different streams
+// do not meet.
 
-__global__ void __launch_bounds__(256) fin_presum_kernel(const float* __restrict__ partial, int P, int C2, int rb) {
-  float* out = g_fin_scratch;
+__global__ void __launch_bounds__(256) fin_presum_kernel(const float* __restrict__ partial, int P, int C2, int rb,
+                                                         float* __restrict__ out) {
   __shared__ double red[256];
   const int p0 = blockIdx.x * rb, p1 = min(P, p0 + rb);
   for (int c0 = 0; c0 < C2; c0 += 256) {
@@ -1056,36 +1054,41 @@ __global__ void __launch_bounds__(256) fin_presum_kernel(const float* __restrict
   }
 }
 
-// long finalize: pre-sum the caller's [P][2][C] rows into the scratch (returns 1, P becomes the scratch rows)
-static int fin_rows(const float* partial, int& P, int C, hipStream_t st) {
-  // measured (scripts/finalize_micro.py): the extra launch pays from P = 6 400 at every C and from P = 3 200 at C >= 256
-  if (!partial || P <= FIN_PMAX || (P <= 2 * FIN_PMAX && C < 256) || (long)FIN_S * 2 * C > FIN_SCRATCH ||
-      fin_presum_off())
-    return 0;
+// The split decision, for the query and the launch alike: 0 = a single-launch finalize, else the scratch floats of
+// the pre-sum (FIN_S rows of 2C). Measured (scripts/finalize_micro.py): the extra launch pays from P = 6 400 at every
+// C and from P = 3 200 at C >= 256.
+extern "C" int adr_bn_finalize_scratch_floats(int P, int C) {
+  if (P <= FIN_PMAX || (P <= 2 * FIN_PMAX && C < 256) || C > 2048 || fin_presum_off()) return 0;
+  return FIN_S * 2 * C;
+}
+
+// long finalize with scratch: pre-sum the caller's [P][2][C] rows into it; returns the rows to reduce (P = their count)
+static const float* fin_rows(const float* partial, int& P, int C, float* scratch, hipStream_t st) {
+  if (!partial || !scratch || !adr_bn_finalize_scratch_floats(P, C)) return partial;
   const int rb = (P + FIN_S - 1) / FIN_S, S = (P + rb - 1) / rb;
-  hipLaunchKernelGGL(fin_presum_kernel, dim3(S), dim3(256), 0, st, partial, P, 2 * C, rb);
+  hipLaunchKernelGGL(fin_presum_kernel, dim3(S), dim3(256), 0, st, partial, P, 2 * C, rb, scratch);
   P = S;
-  return 1;
+  return scratch;
 }
 
 extern "C" int adr_bn_finalize(const float* partial, int P, int C, double count, const float* gamma, const float* beta,
                                float* running_mean, float* running_var, float momentum, float eps, int training,
-                               float* scale, float* shift, float* mean, float* rstd, void* stream) {
+                               float* scale, float* shift, float* mean, float* rstd, float* scratch, void* stream) {
   ADR_REQUIRE(C > 0, "bn_finalize: C");
   hipStream_t st = (hipStream_t)stream;
-  const int pre = training ? fin_rows(partial, P, C, st) : 0;
+  if (training) partial = fin_rows(partial, P, C, scratch, st);
   hipLaunchKernelGGL(bn_finalize_kernel, dim3(C), dim3(256), 0, st, partial, P, C, count, gamma, beta,
-                     running_mean, running_var, momentum, eps, training, scale, shift, mean, rstd, pre);
+                     running_mean, running_var, momentum, eps, training, scale, shift, mean, rstd);
   return check_launch("adr_bn_finalize");
 }
 
 extern "C" int adr_bn_bwd_finalize(const float* partial, int P, int C, double count, const float* mean,
                                    const float* rstd, const float* gamma, float* dgamma, float* dbeta, float* A,
-                                   float* B, float* Cc, int training, int accumulate, void* stream) {
+                                   float* B, float* Cc, int training, int accumulate, float* scratch, void* stream) {
   hipStream_t st = (hipStream_t)stream;
-  const int pre = fin_rows(partial, P, C, st);
+  partial = fin_rows(partial, P, C, scratch, st);
   hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3(C), dim3(256), 0, st, partial, P, C, count, mean,
-                     rstd, gamma, dgamma, dbeta, A, B, Cc, training, accumulate, pre);
+                     rstd, gamma, dgamma, dbeta, A, B, Cc, training, accumulate);
   return check_launch("adr_bn_bwd_finalize");
 }
 
