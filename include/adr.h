@@ -560,7 +560,12 @@ int adr_dcn_bwd_bf16_levels(const adr_dcn_level* lv, int levels, int xcs, int om
  * records (4 tiles {int64 byte offset; int sw, x1a, y1a, x2a, y2a, x1b, y1b}, then int ntile, cw, ch, warp,
  * tab_off, lut_off, flip_ud, flip_lr, rgb, pad; size adr_augment_desc_size()); tables: per warped image adelta[W],
  * bdelta[W], X0[H], Y0[H] (cv::warpAffine fixed point, from the host); luts: 768 bytes (hue, sat, val) per image
- * with HSV (lut_off -1: none). Random draws, matrices and labels stay on the host (adrefine/data/augment.py). */
+ * with HSV (lut_off -1: none). Random draws, matrices and labels stay on the host (adrefine/data/augment.py).
+ * warp: 0 none, 1 warpAffine (the tables above), 2 warpPerspective (RandomPerspective with perspective > 0): tab_off
+ * is then even (8-byte aligned) and points at nine doubles inside `tables`, the float32 3x3 matrix inverted in double
+ * as cv::invert does (from the host); the kernel evaluates cv::warpPerspective's per-pixel arithmetic in double (block
+ * origin, W = W0 + t6*x1, 32 / W by IEEE division or 0 when W == 0, int clamp, rint, short clamp). Restated from
+ * OpenCV 4.x's published algorithm: PARITY UNPINNED against real OpenCV, as the affine warp is. */
 int adr_augment_u8(const void* pool, const void* descs, int B, const int* tables, const void* luts, void* out, int H,
                    int W, void* stream);
 int adr_augment_desc_size(void);

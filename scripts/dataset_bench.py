@@ -3,11 +3,14 @@ resident sources against the same plans rendered from host numpy sources (the pa
 throughput beside a training step. No number is promised; the one requirement is (c): the resident path is not slower
 than the host-source path of the same run on the same device.
 
-  python scripts/dataset_bench.py [--out profiles/dataset_bench.json] [--n 512] [--mixup P]   (run it under `timeout`)
+  python scripts/dataset_bench.py [--out profiles/dataset_bench.json] [--n 512] [--mixup P] [--perspective P]
+  (run it under `timeout`)
 
 --mixup P (default 0: the rows as they have always been measured) sets hyp.mixup: a sample is then mixed with
 probability P (two layers, adr_augment_mix_u8). With P > 0 the result does not replace the file: it is stored in it
-under the key "mixup_P", next to the existing rows.
+under the key "mixup_P", next to the existing rows. --perspective P (default 0) sets hyp.perspective: every image is
+then warped by cv2.warpPerspective's arithmetic (AugDesc.warp == 2) instead of warpAffine's tables; the result is stored
+under the key "perspective_P" in the same way (with both, under "mixup_P_perspective_P").
 
 Input: a synthetic directory of --n PNGs around 1280 x 720 (five sizes) with 1-8 labels each, written to a temporary
 directory; imgsz 640, batch 64, the default hyp. Medians of 20 batches after 3 warm-ups, HIP events and host wall
@@ -81,6 +84,8 @@ def main():
     ap.add_argument("--n", type=int, default=512)
     ap.add_argument("--no-train", action="store_true", help="skip (d)")
     ap.add_argument("--mixup", type=float, default=0.0, help="hyp.mixup; > 0: stored under the key mixup_P")
+    ap.add_argument("--perspective", type=float, default=0.0,
+                    help="hyp.perspective; > 0: stored under the key perspective_P")
     args = ap.parse_args()
     assert torch.cuda.is_available(), "dataset_bench needs the GPU"
     from recipe import AUG_HYPS
@@ -90,11 +95,13 @@ def main():
     from adrefine.data.dataset import YOLODataset, load_bgr
     from adrefine.data.pool import DevicePool
 
-    hyp = lambda: SimpleNamespace(**dict(AUG_HYPS["default"], mixup=args.mixup), mask_ratio=4,  # noqa: E731
-                                  overlap_mask=True)
+    hyp = lambda: SimpleNamespace(**dict(AUG_HYPS["default"], mixup=args.mixup,  # noqa: E731
+                                         perspective=args.perspective), mask_ratio=4, overlap_mask=True)
     res = {"imgsz": IMGSZ, "batch": BS, "images": args.n, "device": torch.cuda.get_device_name(0)}
     if args.mixup > 0:
         res["mixup"] = args.mixup
+    if args.perspective > 0:
+        res["perspective"] = args.perspective
     with tempfile.TemporaryDirectory() as tmp:
         t0 = time.perf_counter()
         tree = write_dataset(Path(tmp) / "syn", args.n)
@@ -190,6 +197,9 @@ def main():
         r_dev = timed([lambda ps=ps: render(ps) for ps in plans])
         r_host = timed([lambda ps=ps: render(ps, "cuda") for ps in hplans])
         r_dev2 = timed([lambda ps=ps: render(ps) for ps in plans])
+        if args.perspective > 0:
+            res["perspective_layers_per_batch"] = statistics.mean(
+                sum(q.P is not None for p in ps for q in p.layers()) for ps in plans)
         if args.mixup > 0:
             res["mixed_samples_per_batch"] = statistics.mean(sum(p.mix is not None for p in ps) for ps in plans)
         res["render_batch"] = {"resident": r_dev, "host_sources": r_host, "resident_again": r_dev2, "identical": same,
@@ -220,8 +230,9 @@ def main():
                 dt = time.perf_counter() - t0
                 res[f"loader_with_step_prefetch{prefetch}"] = {"images_per_s": nimg / dt, "ms_per_batch": dt / (nimg / BS) * 1e3}
     Path(args.out).parent.mkdir(parents=True, exist_ok=True)
-    if args.mixup > 0 and Path(args.out).exists():  # beside the mixup 0 rows, which stay as they were measured
-        res = dict(json.loads(Path(args.out).read_text()), **{f"mixup_{args.mixup:g}": res})
+    key = "_".join(f"{k}_{v:g}" for k, v in (("mixup", args.mixup), ("perspective", args.perspective)) if v > 0)
+    if key and Path(args.out).exists():  # beside the default-hyp rows, which stay as they were measured
+        res = dict(json.loads(Path(args.out).read_text()), **{key: res})
     Path(args.out).write_text(json.dumps(res, indent=1) + "\n")
     print(json.dumps(res))
 

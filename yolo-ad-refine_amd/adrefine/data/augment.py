@@ -4,15 +4,16 @@ the GPU.
 The transforms keep the reference's classes, constructor arguments, RNG calls (python `random` / `np.random`, same
 order, same count) and label arithmetic (numpy, bit-identical boxes through adrefine.data.instance). What they do
 NOT do is touch pixels: `labels["img"]` is an ImagePlan — the recipe of the image (mosaic tiles over source images,
-the warpAffine matrix, MixUp's second layer and ratio, the HSV LUTs, the flips, the channel order) — and `collate_fn`
-renders the whole batch with one launch of adr_augment_u8, or of adr_augment_mix_u8 when a sample of it is mixed
+the warpAffine or warpPerspective matrix, MixUp's second layer and ratio, the HSV LUTs, the flips, the channel order)
+— and `collate_fn` renders the whole batch with one launch of adr_augment_u8, or of adr_augment_mix_u8 when a sample of it is mixed
 (csrc/adr_augment.hip), straight into the uint8 (B, 3, H, W) tensor the trainer reads
 (FusedTrainer takes uint8 batches, /255 in the stem). The 2s x 2s mosaic canvas, the warped and the HSV images of
 the reference never exist.
 
 Covered (detection, the default hyp of cfg/default.yaml and any degrees / translate / scale / shear / flip / HSV
-gains): Mosaic (n=4), CopyPaste (p=0 or no segments), RandomPerspective (perspective 0: warpAffine), MixUp (any p:
-the second sample through the same pre_transform, np.random.beta(32, 32), labels concatenated, the float64 blend
+gains): Mosaic (n=4), CopyPaste (p=0 or no segments), RandomPerspective (perspective 0: warpAffine; perspective > 0:
+warpPerspective, the float32 3x3 inverted in double on the host as cv::invert does, the per-pixel division in the
+kernel), MixUp (any p: the second sample through the same pre_transform, np.random.beta(32, 32), labels concatenated, the float64 blend
 (img1 * r + img2 * (1 - r)).astype(np.uint8) evaluated per pixel by the kernel, two products and a sum without FMA,
 truncated), Albumentations (absent package: no-op, as in the reference without albumentations installed), RandomHSV,
 RandomFlip, Format; LetterBox (every constructor argument; rect_shape, ratio_pad and the label update), as
@@ -22,7 +23,7 @@ A LetterBox that only pads (the shape already equals new_unpad: every dataset-fe
 BaseDataset.load_image leaves the long side at imgsz) is a canvas with one tile and goes through adr_augment_u8 with
 the rest of the chain; a LetterBox that resizes is rendered by adr_letterbox_u8 (csrc/adr_letterbox.hip: cv2.resize
 INTER_LINEAR in OpenCV's fixed point + constant border + RGB / CHW). Not covered (raise): a LetterBox resize followed
-by warp / HSV / flip in one plan (cannot arise from a dataset), warpPerspective, CopyPaste with p > 0, mosaic9,
+by warp / HSV / flip in one plan (cannot arise from a dataset), CopyPaste with p > 0, mosaic9,
 segments / keypoints. Source images come in resized as BaseDataset.load_image leaves them (data/base.py:151-190): host arrays (uploaded with the batch), or DeviceImages of one data/pool.py DevicePool,
 decoded on the host once, resized by adr_resize_u8 and resident in HBM (data/dataset.py YOLODataset): then a batch
 uploads descriptors and tables only."""
@@ -40,14 +41,15 @@ from .instance import Instances
 
 __all__ = ["ImagePlan", "Compose", "Mosaic", "CopyPaste", "RandomPerspective", "MixUp", "Albumentations", "RandomHSV",
            "RandomFlip", "LetterBox", "Format", "v8_transforms", "build_transforms", "close_mosaic", "collate_fn",
-           "render", "render_letterbox", "warp_affine_tables", "resize_linear_tables"]
+           "render", "render_letterbox", "warp_affine_tables", "warp_perspective_matrix", "resize_linear_tables"]
 
 
 class ImagePlan:
     """A deferred uint8 BGR HWC image (see the module docstring). Stages must come in the chain's order:
     canvas (source / mosaic / letterbox) -> warp -> mix -> hsv -> flips -> channel order. A letterbox that resizes is
     a stage of its own (`resize`), followed by the channel order only. The mix stage (MixUp) holds a second layer: a
-    plan of the same size with a canvas and at most a warp."""
+    plan of the same size with a canvas and at most a warp. The warp is M (warpAffine) or P (warpPerspective), never
+    both; every stage rule treats them alike."""
 
     def __init__(self, src: np.ndarray):
         if src.dtype != np.uint8 or src.ndim != 3 or src.shape[2] != 3:
@@ -59,6 +61,7 @@ class ImagePlan:
         self.resize = None  # (nw, nh, left, top): LetterBox's cv2.resize of the canvas to (nw, nh), placed at (left, top)
         self.ratio_pad = None  # LetterBox: ((ratio_w, ratio_h), (left, top))
         self.M = None  # 2x3 float32 warpAffine matrix (canvas -> output)
+        self.P = None  # 3x3 float32 warpPerspective matrix (canvas -> output); at most one of M and P
         self.mix = None  # MixUp: (second layer ImagePlan, r, 1 - r), both ratios float64 from the host
         self.lut = None  # (3, 256) uint8
         self.flip_ud = self.flip_lr = False
@@ -97,7 +100,8 @@ class ImagePlan:
     def letterbox(self, new_unpad, left, top, right, bottom):
         """The plan of cv2.copyMakeBorder(cv2.resize(image, new_unpad) if its size differs, top, bottom, left, right,
         114) (LetterBox, augment.py:1583-1589) — a new plan; this one is unchanged."""
-        self._stage(self.M is None and self.lut is None and not (self.flip_ud or self.flip_lr), "letterbox")
+        self._stage(self.M is None and self.P is None and self.lut is None and not (self.flip_ud or self.flip_lr),
+                    "letterbox")
         q = copy.copy(self)
         w, h = self.size
         nw, nh = (int(v) for v in new_unpad)
@@ -222,8 +226,8 @@ class Mosaic(BaseMixTransform):
         for i in range(4):
             patch = labels if i == 0 else labels["mix_labels"][i - 1]
             src = _plan(patch["img"])
-            if len(src.tiles) != 1 or src.M is not None or src.lut is not None or src.resize is not None \
-                    or src.mix is not None:
+            if len(src.tiles) != 1 or src.M is not None or src.P is not None or src.lut is not None \
+                    or src.resize is not None or src.mix is not None:
                 raise NotImplementedError("Mosaic tiles must be untransformed source images")
             img = src.tiles[0][0]
             h, w = patch.pop("resized_shape")
@@ -319,7 +323,9 @@ class Albumentations:
 
 
 class RandomPerspective:
-    """augment.py:951-1298 with perspective 0 (cv2.warpAffine)."""
+    """augment.py:951-1298: perspective 0 plans cv2.warpAffine (plan.M = M[:2]), perspective != 0 plans
+    cv2.warpPerspective (plan.P = M, the whole float32 3x3); the draws and the box arithmetic are the same either
+    way, as in the reference."""
 
     def __init__(self, degrees=0.0, translate=0.1, scale=0.5, shear=0.0, perspective=0.0, border=(0, 0),
                  pre_transform=None):
@@ -346,10 +352,12 @@ class RandomPerspective:
         T[1, 2] = random.uniform(0.5 - self.translate, 0.5 + self.translate) * self.size[1]
         M = T @ S @ R @ P @ C
         if (border[0] != 0) or (border[1] != 0) or (M != np.eye(3)).any():
+            img._stage(img.M is None and img.P is None and img.lut is None and not (img.flip_ud or img.flip_lr),
+                       "warp")
             if self.perspective:
-                raise NotImplementedError("RandomPerspective with perspective != 0 (warpPerspective)")
-            img._stage(img.M is None and img.lut is None and not (img.flip_ud or img.flip_lr), "warp")
-            img.M = M[:2].copy()
+                img.P = M.copy()  # cv2.warpPerspective(img, M): the whole matrix, its third row included
+            else:
+                img.M = M[:2].copy()
             img.size = tuple(self.size)
         return img, M, s
 
@@ -628,6 +636,22 @@ def warp_affine_tables(M, dsize):
             np.rint((m[4] * ys + m[5]) * 1024).astype(np.int64) + 16)
 
 
+def warp_perspective_matrix(P):
+    """The nine coefficients cv::warpPerspective iterates with (imgwarp.cpp, restated: PARITY UNPINNED against real
+    OpenCV): the float32 3x3 matrix converted to double and inverted by cv::invert's closed 3x3 form (determinant by
+    the first row, d = 1 / det, the adjugate's entries times d; a zero determinant gives the zero matrix), every
+    product and difference rounded on its own (Python floats: no FMA). Returns a float64 array of 9."""
+    m00, m01, m02, m10, m11, m12, m20, m21, m22 = (float(v) for v in np.asarray(P, dtype=np.float32).reshape(9))
+    det = m00 * (m11 * m22 - m12 * m21) - m01 * (m10 * m22 - m12 * m20) + m02 * (m10 * m21 - m11 * m20)
+    if det == 0:
+        return np.zeros(9, dtype=np.float64)
+    d = 1.0 / det
+    return np.array([(m11 * m22 - m12 * m21) * d, (m02 * m21 - m01 * m22) * d, (m01 * m12 - m02 * m11) * d,
+                     (m12 * m20 - m10 * m22) * d, (m00 * m22 - m02 * m20) * d, (m02 * m10 - m00 * m12) * d,
+                     (m10 * m21 - m11 * m20) * d, (m01 * m20 - m00 * m21) * d, (m00 * m11 - m01 * m10) * d],
+                    dtype=np.float64)
+
+
 class _Tile(ctypes.Structure):
     _fields_ = [("off", ctypes.c_int64)] + [(n, ctypes.c_int) for n in ("sw", "x1a", "y1a", "x2a", "y2a", "x1b", "y1b")]
 
@@ -695,6 +719,8 @@ def render(plans, device="cuda", out=None):
             t.off, t.sw = index[key], src.shape[1]
             t.x1a, t.y1a, t.x2a, t.y2a, t.x1b, t.y1b = x1a, y1a, x2a, y2a, x1b, y1b
         d.cw, d.ch = p.canvas
+        if p.M is not None and p.P is not None:
+            raise ValueError("render: a plan has a warpAffine and a warpPerspective matrix")
         d.warp = int(p.M is not None)
         if p.M is not None:
             tab = np.concatenate(warp_affine_tables(p.M, (W, H)))
@@ -703,6 +729,16 @@ def render(plans, device="cuda", out=None):
             d.tab_off = ntab
             tabs.append(tab.astype(np.int32))
             ntab += tab.size
+        elif p.P is not None:  # warp 2: nine doubles inside the int tables, at an even (8-byte aligned) offset
+            t = warp_perspective_matrix(p.P)
+            if not np.isfinite(t).all():
+                raise ValueError("render: the inverse of a warpPerspective matrix is not finite")
+            if ntab & 1:
+                tabs.append(np.zeros(1, np.int32))
+                ntab += 1
+            d.warp, d.tab_off = 2, ntab
+            tabs.append(t.view(np.int32))
+            ntab += 18
         d.lut_off = -1
 
     for b, p in enumerate(plans):
@@ -752,7 +788,7 @@ LB_COPY, LB_LINEAR, LB_AREA2 = 0, 1, 2
 
 def _letterbox_geometry(p):
     """(src, nw, nh, left, top) of a plan adr_letterbox_u8 can render; src None: nothing but the 114 fill."""
-    if p.M is not None or p.lut is not None or p.flip_ud or p.flip_lr or len(p.tiles) > 1 or p.mix is not None:
+    if p.M is not None or p.P is not None or p.lut is not None or p.flip_ud or p.flip_lr or len(p.tiles) > 1 or p.mix is not None:
         raise ValueError("render_letterbox: the plan has mosaic / warp / mix / HSV / flip stages (render() takes "
                          "those)")
     if not p.tiles:

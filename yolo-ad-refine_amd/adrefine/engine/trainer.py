@@ -40,6 +40,7 @@ range), so no loss scaling is needed and the GradScaler is the identity.
 from __future__ import annotations
 
 import ctypes
+import gc
 import math
 import os
 import random
@@ -522,31 +523,43 @@ class FusedTrainer:
         torch.cuda.current_stream().wait_stream(s)
         for t, v in zip(bufs, saved):
             t.copy_(v)
-        nst = len(self.cuts) + 1
-        g_stages = [torch.cuda.CUDAGraph() for _ in range(nst)]
-        cm = [torch.cuda.graph(g_stages[0], capture_error_mode=_CAPTURE_MODE)]
-        cm[0].__enter__()
-        nxt = [1]
-
-        def after_stage(s):  # close this stage's graph, open the next one on the same memory pool
-            cm[0].__exit__(None, None, None)
-            if nxt[0] < nst:
-                cm[0] = torch.cuda.graph(g_stages[nxt[0]], pool=g_stages[0].pool(), capture_error_mode=_CAPTURE_MODE)
-                nxt[0] += 1
-                cm[0].__enter__()
-
+        # torch.cuda.graph no longer collects garbage before a capture (torch >= 2.9). A dead reference cycle that
+        # owns captured graphs and their pools (a dropped trainer, for one) must not be finalised by a collection
+        # that happens to fire while this thread's stream is capturing: collect now, and keep the cyclic collector
+        # off until the last graph of the step is closed
+        gc.collect()
+        gc_was_on = gc.isenabled()
+        gc.disable()
         try:
-            items = self.forward_backward(self.static_batch, after_stage)
-        except BaseException:
-            if nxt[0] <= nst:
-                try:
-                    cm[0].__exit__(None, None, None)
-                except Exception:  # noqa: BLE001 - capture already broken; surface the original error
-                    pass
-            raise
-        g_opt = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g_opt, pool=g_stages[0].pool(), capture_error_mode=_CAPTURE_MODE):
-            self._opt()
+            nst = len(self.cuts) + 1
+            g_stages = [torch.cuda.CUDAGraph() for _ in range(nst)]
+            cm = [torch.cuda.graph(g_stages[0], capture_error_mode=_CAPTURE_MODE)]
+            cm[0].__enter__()
+            nxt = [1]
+
+            def after_stage(s):  # close this stage's graph, open the next one on the same memory pool
+                cm[0].__exit__(None, None, None)
+                if nxt[0] < nst:
+                    cm[0] = torch.cuda.graph(g_stages[nxt[0]], pool=g_stages[0].pool(),
+                                             capture_error_mode=_CAPTURE_MODE)
+                    nxt[0] += 1
+                    cm[0].__enter__()
+
+            try:
+                items = self.forward_backward(self.static_batch, after_stage)
+            except BaseException:
+                if nxt[0] <= nst:
+                    try:
+                        cm[0].__exit__(None, None, None)
+                    except Exception:  # noqa: BLE001 - capture already broken; surface the original error
+                        pass
+                raise
+            g_opt = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(g_opt, pool=g_stages[0].pool(), capture_error_mode=_CAPTURE_MODE):
+                self._opt()
+        finally:
+            if gc_was_on:
+                gc.enable()
         self.graphs = (g_stages, g_opt, items)
         # a larger capacity holds every batch a smaller one held: drop the smaller sets, so graph memory stays at
         # ONE captured step (each set owns a private pool with a whole step's activations) however many buckets a

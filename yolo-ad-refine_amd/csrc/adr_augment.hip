@@ -2,7 +2,8 @@
 // pixel of every image of the batch, the fused chain
 //
 //   Mosaic canvas (four resized sources placed around the mosaic centre, 114 elsewhere; augment.py:657-713)
-//   -> RandomPerspective's cv2.warpAffine (INTER_LINEAR, border 114; augment.py:1016-1077)
+//   -> RandomPerspective's cv2.warpAffine, or cv2.warpPerspective when the hyp sets `perspective` (INTER_LINEAR,
+//      border 114; augment.py:1016-1077)
 //   -> MixUp with a second such layer (float64 blend, truncated; augment.py:926-948; adr_augment_mix_u8 only)
 //   -> RandomHSV (BGR -> HSV, per-channel LUTs, HSV -> BGR; augment.py:1344-1378)
 //   -> RandomFlip up-down / left-right (index mirrors; augment.py:1429-1472)
@@ -12,7 +13,8 @@
 // Canvas pixels are looked up in the tile table (source pixel or 114) when the warp's bilinear taps read them.
 // The host draws every random parameter in the reference's order and supplies the integer tables of the chain:
 // the warp's fixed-point source coordinates (cv::warpAffine's AB_BITS 10 / INTER_BITS 5 arithmetic, computed in
-// double on the host exactly as OpenCV does) and the three HSV LUTs; the kernel is integer arithmetic plus the
+// double on the host exactly as OpenCV does; for warpPerspective the inverted matrix, whose per-pixel division the
+// kernel does in double as OpenCV does) and the three HSV LUTs; the kernel is integer arithmetic plus the
 // float32 HSV -> BGR of OpenCV's 8U path (contraction off, round half to even). One thread per output pixel: the
 // three plane stores are coalesced, the bilinear taps read neighbouring source pixels (L2 hits).
 #include "adr_common.h"
@@ -33,8 +35,8 @@ struct AugDesc {
   AugTile tile[4];
   int ntile;
   int cw, ch;       // canvas size
-  int warp;         // 1: warpAffine tables at tab_off (adelta[W], bdelta[W], X0[H], Y0[H])
-  int tab_off;
+  int warp;         // 1: warpAffine tables at tab_off (adelta[W], bdelta[W], X0[H], Y0[H]); 2: warpPerspective, the
+  int tab_off;      // nine doubles of the inverted matrix at tab_off (even: 8-byte aligned)
   int lut_off;      // -1: no HSV; else 768 bytes (hue, sat, val)
   int flip_ud, flip_lr, rgb;
   int pad_;
@@ -109,14 +111,48 @@ __device__ __forceinline__ void hsv2bgr(int hi, int si, int vi, int out[3]) {
   }
 }
 
-// One layer of the chain at output pixel (xs, ys) (already mirrored): the canvas pixel, or cv::warpAffine's
-// fixed-point bilinear of its four canvas taps, clamped. Shared by the plain and the MixUp kernel.
+// cv::warpPerspective's source coordinate of output pixel (xs, ys) in INTER_BITS (5) fixed point (imgwarp.cpp
+// WarpPerspectiveInvoker, restated: PARITY UNPINNED against real OpenCV). t: the nine doubles of the inverted matrix.
+// OpenCV walks the output in blocks bw0 wide and evaluates the row's X0 / Y0 / W0 at the block's origin bx, then adds
+// t * x1 per pixel: t0 * bx + t0 * x1 rounds differently from t0 * xs, so the block origin is part of the arithmetic.
+// All in double, no contraction, true IEEE divisions; std::min / std::max as the comparisons they are.
+__device__ __forceinline__ void perspective_xy(const double* t, int xs, int ys, int H, int W, int& X, int& Y) {
+  const int bh0 = min(16, H), bw0 = min(1024 / bh0, W);
+  const int bx = (xs / bw0) * bw0, x1 = xs - bx;
+  const double X0 = (t[0] * bx + t[1] * ys) + t[2], Y0 = (t[3] * bx + t[4] * ys) + t[5],
+               W0 = (t[6] * bx + t[7] * ys) + t[8];
+  double w = W0 + t[6] * x1;
+  w = w != 0. ? 32. / w : 0.;  // INTER_TAB_SIZE / W
+  double fX = (X0 + t[0] * x1) * w, fY = (Y0 + t[3] * x1) * w;
+  fX = fX < 2147483647. ? fX : 2147483647.;
+  fX = -2147483648. < fX ? fX : -2147483648.;
+  fY = fY < 2147483647. ? fY : 2147483647.;
+  fY = -2147483648. < fY ? fY : -2147483648.;
+  X = (int)__builtin_rint(fX);  // round half to even
+  Y = (int)__builtin_rint(fY);
+}
+
+__device__ __forceinline__ int clamp_short(int v) { return v < -32768 ? -32768 : (v > 32767 ? 32767 : v); }
+
+// One layer of the chain at output pixel (xs, ys) (already mirrored): the canvas pixel, or the fixed-point bilinear
+// of its four canvas taps, clamped, at cv::warpAffine's (warp 1) or cv::warpPerspective's (warp 2) source coordinate.
+// Shared by the plain and the MixUp kernel.
 __device__ __forceinline__ void layer_px(const uint8_t* pool, const AugDesc& d, const int* tabs, int xs, int ys,
                                          int H, int W, int bgr[3]) {
   if (d.warp) {
     const int* t = tabs + d.tab_off;
-    const int X = (t[2 * W + ys] + t[xs]) >> 5, Y = (t[2 * W + H + ys] + t[W + xs]) >> 5;
-    const int sx = X >> 5, sy = Y >> 5, fx = X & 31, fy = Y & 31;
+    int X, Y, sx, sy;
+    if (d.warp == 2) {
+      perspective_xy(reinterpret_cast<const double*>(t), xs, ys, H, W, X, Y);
+      sx = clamp_short(X >> 5);  // saturate_cast<short>
+      sy = clamp_short(Y >> 5);
+    } else {
+      X = (t[2 * W + ys] + t[xs]) >> 5;
+      Y = (t[2 * W + H + ys] + t[W + xs]) >> 5;
+      sx = X >> 5;
+      sy = Y >> 5;
+    }
+    const int fx = X & 31, fy = Y & 31;
     int v00[3], v01[3], v10[3], v11[3];
     canvas_px(pool, d, sx, sy, v00);
     canvas_px(pool, d, sx + 1, sy, v01);
