@@ -392,6 +392,47 @@ def grads_fixtures(tasks, block, conv, head, uloss, uops, note):
          "nn/tasks.py:290-302, utils/loss.py:419-520, head.py:1049-1252", True)
 
 
+def loss_edge_fixtures(tasks, block, conv, head, uloss, uops, note):
+    """The reference's v8DetectionLoss on the edge-case scenarios of tests/loss_util.py (trained regime on a
+    non-square image; exact ties): loss, items, n_fg (from the assigner's own fg mask), the per-level gradient norms
+    and the full gradient. Recorded numbers only; the scenario inputs are rebuilt from their seeds by the tests."""
+    sys.path.insert(0, str(REPO / "tests"))
+    import loss_util as LU
+
+    hd = head.AYHead(80, [128, 128, 128])
+    hd.stride = torch.tensor([8.0, 16.0, 32.0])
+
+    class _M(torch.nn.Module):
+        def __init__(s):
+            super().__init__()
+            s.model = torch.nn.ModuleList([hd])
+            s.args = _hyp()
+
+    crit = uloss.v8DetectionLoss(_M())
+    seen = {}
+    assign = crit.assigner.forward
+
+    def spy(*a, **k):
+        out = assign(*a, **k)
+        seen["n_fg"] = int(out[3].sum())
+        return out
+    crit.assigner.forward = spy
+    for name in LU.GOLDEN:
+        feats, batch, nc, (H, W) = LU.scenario(name)
+        assert nc == 80
+        fs = [f.clone().requires_grad_(True) for f in feats]
+        loss, items = crit(fs, {k: v.clone() for k, v in batch.items()})
+        loss.backward()
+        d = {"loss": _np(loss), "items": _np(items), "n_fg": np.array(seen["n_fg"]), "imgsz": np.array([H, W])}
+        for i, f in enumerate(fs):
+            d[f"gfeat{i}"] = _np(f.grad).astype(np.float32)
+            d[f"gfeat{i}_norm"] = np.array(float(f.grad.norm()))
+        np.savez_compressed(OUT / f"loss_edge_{name}.npz", **d)
+        note(f"loss_edge_{name}", f"v8DetectionLoss on tests/loss_util.scenario('{name}') ({H}x{W}, bs {fs[0].shape[0]})",
+             "utils/loss.py:419-520, tal.py:39-265, metrics.py:74-125,539-564")
+        print(name, float(loss), seen["n_fg"], (OUT / f"loss_edge_{name}.npz").stat().st_size)
+
+
 def metrics_fixtures(tasks, block, conv, head, uloss, uops, note):
     """Validator metrics tail on synthetic detections: per-image box_iou (utils/metrics.py:52) + greedy
     match_predictions (engine/validator.py:221) -> tp (N, 10); ap_per_class (metrics.py:1144) + Metric

@@ -47,13 +47,22 @@ def test_loss_fixture(S, bs):
 
 
 def test_loss_bf16_close():
+    """bf16 head outputs: within 3 % of the fp32 fixture (the distance is the rounding of the inputs), and within
+    loss_util.BF16_LOSS_RTOL of the oracle evaluated on the same bf16-rounded inputs (what the kernel itself adds)."""
+    import adr_oracle as O
     from adrefine.utils.loss import v8DetectionLoss
+    from loss_util import BF16_LOSS_RTOL
     g = golden("loss_320_bs4")
     _, fd = _feats(320, 4, int(g["feat0_seed"][0]), torch.bfloat16)
     crit = v8DetectionLoss(_M())
     batch = {k: torch.from_numpy(g[k]) for k in ("batch_idx", "cls", "bboxes")}
     loss, items = crit(fd, batch)
     assert abs(float(loss) - float(g["loss"])) <= 0.03 * float(g["loss"])
+    ref, _ = O.detection_loss([f.detach().float().cpu().contiguous() for f in fd], batch["batch_idx"], batch["cls"],
+                              batch["bboxes"])
+    d = abs(float(loss) - float(ref)) / float(ref)
+    print(f"[loss-edges] bf16 loss_320_bs4: loss rel {d:.3e}")
+    assert d <= BF16_LOSS_RTOL, d
 
 
 _YAMLS = {"701": "yolo11-701-YOLO-AD-Refine.yaml", "697": "yolo11-697-newfpn+mona+AYHead+mlca3.yaml"}

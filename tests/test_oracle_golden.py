@@ -210,6 +210,23 @@ def test_loss_fixture(S, bs):
             _close(f.grad, g[f"gfeat{i}"], rtol=1e-5, atol=1e-7)
 
 
+@pytest.mark.parametrize("name", ["trained_nonsquare", "exact_ties"])
+def test_loss_edge_fixture(name):
+    """The edge-case scenarios of tests/loss_util.py that carry a reference fixture (the trained regime on a 160 x 256
+    image; exact ties in min / max / clamp and in the top-10 cut), at test_loss_fixture's tolerances."""
+    import loss_util as LU
+    g = golden(f"loss_edge_{name}")
+    o = LU.oracle(name)
+    _close(o["loss"], g["loss"], rtol=1e-5)
+    _close(o["items"], g["items"], rtol=1e-5, atol=1e-6)
+    assert o["n_fg"] == int(g["n_fg"])
+    for i, gr in enumerate(o["grads"]):
+        assert abs(float(gr.norm()) - float(g[f"gfeat{i}_norm"])) <= 1e-5 * float(g[f"gfeat{i}_norm"]) + 1e-7
+        _close(gr, g[f"gfeat{i}"], rtol=1e-5, atol=1e-7)
+    ref_fg = LU.box_grad_rows([torch.from_numpy(g[f"gfeat{i}"]) for i in range(3)], 80)
+    assert torch.equal(ref_fg, o["fg"])  # the reference's box gradients sit on the oracle's positives
+
+
 @pytest.mark.parametrize("name", ["predict", "val", "tight"])
 def test_nms_fixture(name):
     g = golden(f"nms_{name}")

@@ -101,6 +101,7 @@ class v8DetectionLoss:  # noqa: N801
         self.nc = m.nc
         self.no = m.nc + m.reg_max * 4
         self.reg_max = m.reg_max
+        self.n_fg = None
         self.gains = (getattr(h, "box", 7.5) if h is not None else 7.5, getattr(h, "cls", 0.5) if h is not None else 0.5,
                       getattr(h, "dfl", 1.5) if h is not None else 1.5)
 
@@ -114,4 +115,5 @@ class v8DetectionLoss:  # noqa: N801
             gt = preprocess_targets(batch["batch_idx"], batch["cls"], batch["bboxes"], B, imgsz)
         gt = gt.to(dev, non_blocking=True).float()
         total, out = DetLossFn.apply(gt, [float(s) for s in self.stride], self.nc, self.gains, *feats)
+        self.n_fg = out[4]  # positives of this call (a device scalar, no synchronisation)
         return total, out[:3]
