@@ -762,7 +762,11 @@ int adr_attn_bwd(int dtype, const void* q, const void* k, const void* v, int cs,
  * f0..f2: the three AYHead train outputs (B, 4*16+nc, Hi, Wi) NHWC; gt: (B, nmax, 5) fp32 device rows
  * [cls, x1, y1, x2, y2] in pixels (the reference's preprocess output, loss.py:392-408; zero rows = padding);
  * g0..g2 receive d(out[3]) / d(f) * grad_scale / B (dense NHWC, row stride 4*16+nc).
- * out (5 floats): box*7.5, cls*0.5, dfl*1.5 (the reference's loss.detach()), (sum)*B, number of positives. */
+ * out (5 floats): box*7.5, cls*0.5, dfl*1.5 (the reference's loss.detach()), (sum)*B, number of positives.
+ * g0 == g1 == g2 == NULL: value-only evaluation (validation losses) — out is computed by the same reductions in
+ * the same order, bit-identical to the call with gradients, and no gradient is stored anywhere; grad_scale is
+ * ignored. Exactly one or two null gradient pointers is an error (nothing is launched). The workspace size is the
+ * same in both modes. */
 size_t adr_det_loss_workspace(int B, int nmax, int A);
 int adr_det_loss(int dtype, const void* f0, const void* f1, const void* f2, int cs0, int cs1, int cs2, int H0, int W0,
                  int H1, int W1, int H2, int W2, float s0, float s1, float s2, int B, int nc, const float* gt,

@@ -24,12 +24,25 @@ class FusedPredictor:
     conf / iou / max_det default to the predictor's (cfg/default.yaml: conf 0.25, iou 0.7, max_det 300); pass the
     validator's conf=0.001, multi_label=True for mAP evaluation. augment=True is the reference's test-time
     augmentation (nn/tasks.py:357-394): three forwards (scale 1, 0.83 left-right flipped, 0.67) merged before the NMS,
-    boxes in the base batch's coordinates — views, forwards, merge and NMS are captured into the one hipGraph."""
+    boxes in the base batch's coordinates — views, forwards, merge and NMS are captured into the one hipGraph.
+
+    keep_feats=True also keeps the eval forward's three raw level maps (B, 4*reg_max + nc, Hi, Wi) — the reference's
+    preds[1], what model.loss(batch, preds) evaluates (engine/validator.py:184): run_padded then returns
+    (out, n, feats), and `feats` holds the last run's maps. After capture() they are the graph's own output tensors
+    (`static_feats`): each replay rewrites them in place, so they stay valid (and are overwritten by the next batch).
+    Without keep_feats nothing of the forward is kept and the graph is the same as before. The reference's TTA
+    returns no level maps (tasks.py:372 `return torch.cat(y, -1), None`), so keep_feats with augment is refused."""
 
     def __init__(self, model, conf=0.25, iou=0.7, max_det=300, agnostic=False, multi_label=False, classes=None,
-                 augment=False):
+                 augment=False, keep_feats=False):
+        if keep_feats and augment:
+            raise ValueError("keep_feats=True with augment=True: test-time augmentation returns no level maps "
+                             "(and the reference computes no loss under it)")
         self.model = model
         self.augment = bool(augment)
+        self.keep_feats = bool(keep_feats)
+        self.feats = None
+        self.static_feats = None
         self.conf, self.iou, self.max_det = conf, iou, max_det
         self.agnostic, self.multi_label, self.classes = agnostic, multi_label, classes
         self.graph = None
@@ -50,9 +63,14 @@ class FusedPredictor:
             y = self.model(img, augment=True) if self.augment else self.model(img)
             if first and self.packs.specs:
                 self.packs.valid = True  # the recording forward packed every operand into the cache
+            if self.keep_feats:
+                if not (isinstance(y, (list, tuple)) and len(y) == 2 and y[1] is not None):
+                    raise RuntimeError("keep_feats=True: the model's eval forward returned no level maps")
+                self.feats = list(y[1])
             y = y[0] if isinstance(y, (list, tuple)) else y
-            return non_max_suppression_padded(y, self.conf, self.iou, self.classes, self.agnostic,
-                                              self.multi_label, self.max_det)
+            res = non_max_suppression_padded(y, self.conf, self.iou, self.classes, self.agnostic,
+                                             self.multi_label, self.max_det)
+            return (*res, self.feats) if self.keep_feats else res
 
     def capture(self, img):
         """Record preprocess + forward + decode + NMS for batches shaped like `img` into one hipGraph (run one
@@ -67,20 +85,22 @@ class FusedPredictor:
         g = torch.cuda.CUDAGraph()
         with torch.cuda.graph(g, capture_error_mode="thread_local"):
             self.static_out = self._run(self.static_in)
+        self.static_feats = self.static_out[2] if self.keep_feats else None
         self.graph = g
 
     def run_padded(self, img):
-        """(out (B, max_det, 6), n (B,) int32) on the device, no host sync."""
+        """(out (B, max_det, 6), n (B,) int32) on the device, no host sync; with keep_feats (out, n, feats)."""
         self.model.eval()
         if self.graph is not None and img.shape == self.static_in.shape and img.dtype == self.static_in.dtype:
             if img.data_ptr() != self.static_in.data_ptr():
                 self.static_in.copy_(img, non_blocking=True)
             self.graph.replay()
+            self.feats = self.static_feats
             return self.static_out
         return self._run(img)
 
     def predict(self, img):
-        out, n = self.run_padded(img)
+        out, n = self.run_padded(img)[:2]
         counts = n.tolist()
         check_counts(counts, out.device)
         return [out[i, :k].clone() for i, k in enumerate(counts)]
@@ -114,7 +134,7 @@ class FusedPredictor:
                 raise ValueError("predict_images: no images")
             dev = next(self.model.parameters()).device
             batch, _ = render_letterbox(imgs, (H, W), device=dev, rgb=True, auto=False)
-        out, n = self.run_padded(batch)
+        out, n = self.run_padded(batch)[:2]
         rows = []
         for i in range(out.shape[0]):
             h0, w0 = imgs[i].shape[:2] if i < len(imgs) else (H, W)

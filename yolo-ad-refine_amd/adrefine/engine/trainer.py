@@ -584,6 +584,30 @@ class FusedTrainer:
                 return self.grad[self._goff[ei]:self._goff[ei] + t.numel()].view(t.shape)
         raise KeyError(name)
 
+    def state_dict(self):
+        """The whole training state in fp32 on the host, for continuing a run bit for bit (engine/fit.py's
+        exact_resume; checkpoint.save_checkpoint keeps the reference's fp16 layout and cannot): the model's
+        state_dict, the EMA, the optimizer moments (momentum, or Adam's exp_avg | exp_avg_sq), the gradient arena
+        (gradients accumulated since the last optimizer step) and the step counters."""
+        return {"model": {k: v.detach().cpu() for k, v in self.model.state_dict().items()},
+                "ema": self.ema_flat.cpu() if self.ema_flat is not None else None,
+                "moments": (self.opt_state if self.adam else self.mom).cpu(), "grad": self.grad.cpu(),
+                "optimizer": self.optimizer, "updates": int(self.updates), "opt_steps": int(self.opt_steps),
+                "ni": int(self.ni), "last_opt_step": int(self.last_opt_step)}
+
+    def load_state_dict(self, state):
+        """Restore state_dict()'s state into a trainer built the same way (same model, optimizer and stages)."""
+        if state["optimizer"] != self.optimizer:
+            raise ValueError(f"trainer state of optimizer {state['optimizer']} does not fit this {self.optimizer}")
+        self.model.load_state_dict({k: v.to(self.dev) for k, v in state["model"].items()}, strict=True)
+        if state["ema"] is not None and self.ema_flat is not None:
+            self.ema_flat.copy_(state["ema"])
+        (self.opt_state if self.adam else self.mom).copy_(state["moments"])
+        self.grad.copy_(state["grad"])
+        self.updates, self.opt_steps = state["updates"], state["opt_steps"]
+        self.ni, self.last_opt_step = state["ni"], state["last_opt_step"]
+        self.packs.valid = False  # weights changed: the next forward repacks
+
     def ema_state_dict(self):
         out = {}
         for ei, (name, t, _, _) in enumerate(self.entries):

@@ -21,6 +21,7 @@ from ..utils.metrics import DetectionStats
 from .predictor import FusedPredictor
 
 RESULT_KEYS = ("metrics/precision(B)", "metrics/recall(B)", "metrics/mAP50(B)", "metrics/mAP50-95(B)", "fitness")
+LOSS_KEYS = ("val/box_loss", "val/cls_loss", "val/dfl_loss")  # label_loss_items(prefix="val"), detect/train.py:109-118
 
 
 class DetectionValidator:
@@ -35,15 +36,31 @@ class DetectionValidator:
     read after the loop.
 
     `model` is the validator's own copy of the network (eval mode; load_ema overwrites its weights). augment=True
-    validates with the reference's test-time augmentation (val(..., augment=True); FusedPredictor(augment=True))."""
+    validates with the reference's test-time augmentation (val(..., augment=True); FusedPredictor(augment=True)).
+
+    compute_loss=True is the validation loss of a training run (engine/validator.py:184, `self.loss +=
+    model.loss(batch, preds)[1]`): after each batch's forward the criterion is evaluated value-only (adr_det_loss
+    without gradients) on the predictor's kept level maps, with targets built from the batch's batch_idx / cls /
+    bboxes at the batch's own image size and zero-padded to FusedTrainer.capacity_bucket rows per image. The three
+    items are summed on the device in fp32 in batch order (adr_axpy, a = 1) and read once after the loop; the
+    results gain 'val/box_loss', 'val/cls_loss', 'val/dfl_loss' = sum / number of batches (validator.py:204,
+    `self.loss.cpu() / len(self.dataloader)`). The loss is timed in a slot of its own, as the reference's dt[2]:
+    'speed' gains 'loss' (ms per image: target preparation, the loss launches and the sum) and the other three
+    slots cover what they cover without compute_loss. Not available with augment=True (TTA keeps no level maps)."""
 
     def __init__(self, model, nc, conf=0.001, iou=0.7, max_det=300, agnostic=False, single_cls=False, cm_conf=None,
-                 augment=False):
+                 augment=False, compute_loss=False):
+        if compute_loss and augment:
+            raise ValueError("compute_loss=True with augment=True: test-time augmentation returns no level maps, "
+                             "and the reference computes no validation loss under it")
         self.model, self.nc = model, nc
         self.single_cls = bool(single_cls)
+        self.compute_loss = bool(compute_loss)
+        self.criterion = None
         # val.py:94-102: multi_label=True, agnostic = single_cls or agnostic_nms
         self.predictor = FusedPredictor(model, conf=conf, iou=iou, max_det=max_det,
-                                        agnostic=bool(agnostic or single_cls), multi_label=True, augment=augment)
+                                        agnostic=bool(agnostic or single_cls), multi_label=True, augment=augment,
+                                        keep_feats=self.compute_loss)
         self.cm_conf = conf if cm_conf is None else cm_conf  # val.py:83 ConfusionMatrix(conf=args.conf)
         self.stats = None
 
@@ -60,27 +77,58 @@ class DetectionValidator:
                 v.copy_(src.to(v.device))
         self.predictor.sync_weights()
 
+    def _batch_loss(self, feats, batch, imgsz, dev):
+        """The batch's three loss items (device, fp32), value-only."""
+        from ..utils.loss import preprocess_targets, v8DetectionLoss
+        from .trainer import FusedTrainer
+        if self.criterion is None:
+            self.criterion = v8DetectionLoss(self.model)
+        gt = preprocess_targets(batch["batch_idx"], batch["cls"], batch["bboxes"], feats[0].shape[0], imgsz)
+        # a fixed row count per capacity bucket: the loss workspace keeps its size from batch to batch; the padded
+        # zero rows are masked out by the assigner (mask_gt), as the trainer's captured steps pad theirs
+        pad = torch.zeros(gt.shape[0], FusedTrainer.capacity_bucket(gt.shape[1]), 5, dtype=torch.float32, device=dev)
+        if gt.shape[1]:
+            pad[:, :gt.shape[1]].copy_(gt, non_blocking=True)
+        with torch.no_grad():
+            return self.criterion(feats, {"gt": pad})[1]
+
     def __call__(self, batches):
+        from .. import kernels as K
+        from ..native import lib
         dev = next(self.model.parameters()).device
         self.stats = stats = DetectionStats(self.nc)
         events = []
+        loss_sum = torch.zeros(3, dtype=torch.float32, device=dev) if self.compute_loss else None
+        nbatches = 0
         for batch in batches:
             img = batch["img"]
             if self.predictor.graph is None:
                 self.predictor.capture(img.to(dev))
-            e = [torch.cuda.Event(enable_timing=True) for _ in range(4)]
+            e = [torch.cuda.Event(enable_timing=True) for _ in range(5 if self.compute_loss else 4)]
             e[0].record()
             img = img.to(dev, non_blocking=True)
             e[1].record()
-            out, n = self.predictor.run_padded(img)
+            out, n = self.predictor.run_padded(img)[:2]
             e[2].record()
+            if self.compute_loss:
+                items = self._batch_loss(self.predictor.feats, batch, tuple(img.shape[2:]), dev).contiguous()
+                lib.adr_axpy(3, 1.0, K.fptr(items), K.fptr(loss_sum), K.stream())
+                nbatches += 1
+                e[4].record()
             stats.update_batched(out, n, batch, imgsz=img.shape[2:], cm_conf=self.cm_conf,
                                  single_cls=self.single_cls)
             e[3].record()
             events.append((e, img.shape[0]))
         res = stats.results()
+        if self.compute_loss:
+            mean = (loss_sum.cpu() / max(nbatches, 1)).tolist()  # the one host read of the losses
+            res.update(zip(LOSS_KEYS, mean))
         torch.cuda.synchronize(dev)
         seen = max(sum(b for _, b in events), 1)
-        ms = [sum(e[i].elapsed_time(e[i + 1]) for e, _ in events) / seen for i in range(3)]
+        # event order per batch: 0 copy 1 forward+NMS 2 [loss 4] scaling+matching 3
+        spans = [(0, 1), (1, 2), (4 if self.compute_loss else 2, 3)]
+        ms = [sum(e[a].elapsed_time(e[b]) for e, _ in events) / seen for a, b in spans]
         res["speed"] = dict(zip(("preprocess", "inference", "postprocess"), ms))
+        if self.compute_loss:
+            res["speed"]["loss"] = sum(e[2].elapsed_time(e[4]) for e, _ in events) / seen
         return res

@@ -87,6 +87,26 @@ class DetLossFn(torch.autograd.Function):
         return (None, None, None, None, *scaled)
 
 
+def det_loss_value(gt, strides, nc, gains, feats):
+    """adr_det_loss with null gradient pointers: the five outputs (box, cls, dfl after gains, sum * B, number of
+    positives) of the same reductions in the same order as the training call, bit for bit; no gradient map is
+    allocated or written, nothing is kept for a backward."""
+    vs = [K.nhwc(f) for f in feats]
+    f0, f1, f2 = feats
+    B, dev = f0.shape[0], f0.device
+    A = sum(f.shape[2] * f.shape[3] for f in feats)
+    nmax = gt.shape[1]
+    wsb = lib.adr_det_loss_workspace(B, nmax, A)
+    ws = torch.empty(wsb // 4 + 16, dtype=torch.float32, device=dev)
+    out = torch.empty(5, dtype=torch.float32, device=dev)
+    gtc = gt.contiguous()
+    lib.adr_det_loss(K.dcode(f0.dtype), *[ctypes.c_void_p(v[1]) for v in vs], *[v[2] for v in vs],
+                     f0.shape[2], f0.shape[3], f1.shape[2], f1.shape[3], f2.shape[2], f2.shape[3],
+                     float(strides[0]), float(strides[1]), float(strides[2]), B, nc, K.fptr(gtc), nmax,
+                     None, None, None, float(B), *[float(x) for x in gains], K.fptr(out), K.fptr(ws), wsb, K.stream())
+    return out
+
+
 class v8DetectionLoss:  # noqa: N801
     """Criterion with the reference's hyper-parameters (box 7.5, cls 0.5, dfl 1.5; TAL topk 10, alpha 0.5,
     beta 6.0; SlideLoss; CIoU/NWD ratio 0.5)."""
@@ -114,6 +134,12 @@ class v8DetectionLoss:  # noqa: N801
         if gt is None:
             gt = preprocess_targets(batch["batch_idx"], batch["cls"], batch["bboxes"], B, imgsz)
         gt = gt.to(dev, non_blocking=True).float()
-        total, out = DetLossFn.apply(gt, [float(s) for s in self.stride], self.nc, self.gains, *feats)
+        strides = [float(s) for s in self.stride]
+        if not torch.is_grad_enabled() or not any(f.requires_grad for f in feats):
+            # nobody can ask for a gradient (validation): the value-only evaluation, same bits in `out`
+            out = det_loss_value(gt, strides, self.nc, self.gains, list(feats))
+            self.n_fg = out[4]
+            return out[3], out[:3]
+        total, out = DetLossFn.apply(gt, strides, self.nc, self.gains, *feats)
         self.n_fg = out[4]  # positives of this call (a device scalar, no synchronisation)
         return total, out[:3]

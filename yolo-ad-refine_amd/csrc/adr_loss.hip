@@ -644,7 +644,11 @@ __global__ void __launch_bounds__(256) loss_scalars_kernel(const float* part, in
 // at once instead of 16 dependent passes per workgroup (a multiple of 16)
 static constexpr int CLS_APB = 32;
 
-template <typename T>
+// GRAD = false is the value-only evaluation (adr_det_loss with null gradient pointers): the same anchors on the same
+// lanes accumulate the same bce * mod terms in the same order and the block tree is unchanged, so part[] (and with it
+// out[]) has the bits of the GRAD = true launch; G is not read, nothing is stored besides part[], and the ltrb lanes
+// (slots 12..15), which only produce gradient rows, idle.
+template <typename T, bool GRAD>
 __global__ void __launch_bounds__(256) loss_cls_grad_kernel(Levels L, Levels G, int B, int nmax, int nc, float gscale,
                                                             const float* gt, const float* pbox, const int* tgi,
                                                             const uint8_t* fg, const float* tnorm, const float* scal,
@@ -664,7 +668,8 @@ __global__ void __launch_bounds__(256) loss_cls_grad_kernel(Levels L, Levels G, 
     int lvl;
     float ax, ay;
     const T* p = feat_row<T>(L, b, a, lvl, ax, ay);
-    T* gp = const_cast<T*>(feat_row<T>(G, b, a, lvl, ax, ay));
+    T* gp = nullptr;
+    if constexpr (GRAD) gp = const_cast<T*>(feat_row<T>(G, b, a, lvl, ax, ay));
     const bool isfg = fg[i] != 0;
     const float nrm = tnorm[i];
     long r = 0;
@@ -697,12 +702,14 @@ __global__ void __launch_bounds__(256) loss_cls_grad_kernel(Levels L, Levels G, 
           const float bce = fmaxf(x[k], 0.f) - x[k] * t + l1p;
           const float mod = (t <= mu - 0.1f) ? 1.f : ((t < mu) ? e21 : __expf(-(t - 1.f)));
           acc += bce * mod;
-          const float sg = x[k] >= 0.f ? r1 : e * r1;
-          g[k] = (sg - t) * mod * cscale;
+          if constexpr (GRAD) {
+            const float sg = x[k] >= 0.f ? r1 : e * r1;
+            g[k] = (sg - t) * mod * cscale;
+          }
         }
-        store8<T>(gp + 4 * RM + c0, g);
+        if constexpr (GRAD) store8<T>(gp + 4 * RM + c0, g);
       }
-    } else {
+    } else if constexpr (GRAD) {
       const int k = slot - 12;
       float gl[RM];
 #pragma unroll
@@ -815,6 +822,11 @@ extern "C" int adr_det_loss(int dtype, const void* f0, const void* f1, const voi
   G.f[0] = g0; G.f[1] = g1; G.f[2] = g2;
   G.cs[0] = 4 * RM + nc; G.cs[1] = 4 * RM + nc; G.cs[2] = 4 * RM + nc;
   int A = L.A;
+  // all three gradient pointers null: value-only (no gradient is stored); a mix is an error before any launch
+  const int nnull = (g0 == nullptr) + (g1 == nullptr) + (g2 == nullptr);
+  ADR_REQUIRE(nnull == 0 || nnull == 3, "det_loss: %d of the 3 gradient pointers are null (pass all, or none for "
+              "the value-only evaluation)", nnull);
+  const bool want_grad = nnull == 0;
   ADR_REQUIRE(ws_bytes >= adr_det_loss_workspace(B, nmax, A), "det_loss: workspace");
   ADR_REQUIRE(cs0 >= 4 * RM + nc && cs1 >= 4 * RM + nc && cs2 >= 4 * RM + nc, "det_loss: head rows too short");
   hipStream_t st = (hipStream_t)stream;
@@ -860,8 +872,17 @@ extern "C" int adr_det_loss(int dtype, const void* f0, const void* f1, const voi
   LDISPATCH(loss_fg_kernel, dim3(nblk), dim3(256), L, B, nmax, gt, pbox, align, tgi, fg, pos, tnorm, part);
   hipLaunchKernelGGL(loss_scalars_kernel, dim3(1), dim3(256), 0, st, part, nblk, scal);
   const int apb = CLS_APB;
-  LDISPATCH(loss_cls_grad_kernel, dim3(cdiv((long)n, apb)), dim3(256), L, G, B, nmax, nc, grad_scale, gt, pbox, tgi, fg,
-            tnorm, scal, part2, box_gain, cls_gain, dfl_gain, apb);
+#define CLS_LAUNCH(T, GRAD)                                                                                  \
+  hipLaunchKernelGGL((loss_cls_grad_kernel<T, GRAD>), dim3(cdiv((long)n, apb)), dim3(256), 0, st, L, G, B, nmax, nc, \
+                     grad_scale, gt, pbox, tgi, fg, tnorm, scal, part2, box_gain, cls_gain, dfl_gain, apb)
+  if (want_grad) {
+    if (dtype == ADR_BF16) CLS_LAUNCH(__bf16, true);
+    else CLS_LAUNCH(float, true);
+  } else {
+    if (dtype == ADR_BF16) CLS_LAUNCH(__bf16, false);
+    else CLS_LAUNCH(float, false);
+  }
+#undef CLS_LAUNCH
   hipLaunchKernelGGL(loss_final_kernel, dim3(1), dim3(256), 0, st, part2, (int)cdiv((long)n, apb), scal, B, box_gain,
                      cls_gain, dfl_gain, out);
 #undef LDISPATCH
