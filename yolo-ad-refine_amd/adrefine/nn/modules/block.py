@@ -307,6 +307,10 @@ class CrossScaleAttentionTSSA(nn.Module):
 
     def forward(self, x):
         B, C, H, W = x.shape
+        for s in self.scales:  # the reference's F.interpolate fails on the empty pooled map; refuse before any launch
+            if H // s == 0 or W // s == 0:
+                raise RuntimeError(f"CrossScaleAttentionTSSA: a {H}x{W} map is smaller than scale {s} "
+                                   f"(pooled size {H // s}x{W // s}); the input image is too small")
         qkvs = []
         xv = list(K.fanout(x, len(self.scales)))
         for s, proj in zip(self.scales, self.qkv_projections):

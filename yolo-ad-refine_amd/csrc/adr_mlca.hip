@@ -398,6 +398,7 @@ extern "C" int adr_mlca_fwd(int dtype, const void* y, int ycs, const void* res, 
                             int H, int W, int C, const float* wl, const float* wg, int k, float local_weight,
                             float* local, float* att, float* sig_l, float* sig_g, void* stream) {
   ADR_REQUIRE(k % 2 == 1 && k <= 15, "mlca: k=%d", k);
+  ADR_REQUIRE(N >= 1 && H >= 1 && W >= 1 && C >= 1, "mlca_fwd: empty map N=%d H=%d W=%d C=%d", N, H, W, C);
   hipStream_t st = (hipStream_t)stream;
   const bool v = mlca_vec(dtype, C, {ycs, rcs, ocs}, {y, res, out});
   MLCA_DISPATCH(dtype, v, mlca_pool_kernel, dim3(LS * LS, N), (const TT*)y, ycs, H, W, C, local);
@@ -419,6 +420,7 @@ extern "C" int adr_mlca_bwd(int dtype, const void* y, int ycs, const void* dout,
                             int H, int W, int C, const float* wl, const float* wg, int k, float local_weight,
                             const float* local, const float* att, const float* sig_l, const float* sig_g, float* dwl,
                             float* dwg, float* ws, size_t ws_bytes, void* stream) {
+  ADR_REQUIRE(N >= 1 && H >= 1 && W >= 1 && C >= 1, "mlca_bwd: empty map N=%d H=%d W=%d C=%d", N, H, W, C);
   ADR_REQUIRE(ws_bytes >= adr_mlca_bwd_workspace(N, C, k), "mlca_bwd: workspace too small");
   hipStream_t st = (hipStream_t)stream;
   float* datt = ws;

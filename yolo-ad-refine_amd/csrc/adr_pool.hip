@@ -1,6 +1,7 @@
 // Pooling / resampling kernels on NHWC views, forward and backward (gather form, deterministic).
-//   * max pool k x k, stride 1, pad k/2 (SPPF, block.py:177-196): first maximum in row-major window order,
-//     as PyTorch's CPU kernel picks it, so gradients route to the same element.
+//   * max pool k x k, stride 1, pad k/2 (SPPF, block.py:177-196): first maximum in row-major window order over the
+//     in-range taps (the first in-range tap when every one is -inf; a NaN wins, the first one met), as PyTorch's CPU
+//     kernel picks it, so gradients route to the same element.
 //   * axis means (row means over W, column means over H) and the separable gate
 //     out = x * a_h[n,h,c] * a_w[n,w,c]  (ELA_HSFPN block.py:1418-1424; CoordAtt head.py:689-707).
 //   * adaptive average pooling, any in/out size (MLCA block.py:1558-1581; CrossScaleAttentionTSSA :2455).
@@ -29,10 +30,13 @@ __global__ void __launch_bounds__(256) maxpool_kernel(const T* x, int xcs, T* y,
     const int c0 = cg * VW;
     float best[VW];
     int bi[VW];
+    // the index starts at the first in-range tap (as ATen's does), so a window of nothing but -inf still routes its
+    // gradient to an element of the image
+    const int first = max(0, p - h) * k + max(0, p - w);
 #pragma unroll
     for (int e = 0; e < VW; ++e) {
       best[e] = -INFINITY;
-      bi[e] = 0;
+      bi[e] = first;
     }
     for (int dy = 0; dy < k; ++dy) {
       const int ih = h - p + dy;
@@ -479,6 +483,12 @@ static dim3 pool_grid(long npix, int G) {
 #define P(t, x) ((t*)(x))
 #define VW_OF(dtype) ((dtype) == ADR_BF16 ? 8 : 4)
 #define GOF(dtype, vec, C) ((C) / ((vec) ? VW_OF(dtype) : 1))
+// sizes no kernel here can compute (an empty map, or a resize from or to one) are refused before any launch
+#define REQUIRE_MAP(who, N, H, W, C) \
+  ADR_REQUIRE((N) >= 1 && (H) >= 1 && (W) >= 1 && (C) >= 1, who ": empty map N=%d H=%d W=%d C=%d", N, H, W, C)
+#define REQUIRE_RESIZE(who, N, H, W, C, OH, OW)                                                                 \
+  ADR_REQUIRE((N) >= 1 && (H) >= 1 && (W) >= 1 && (C) >= 1 && (OH) >= 1 && (OW) >= 1,                           \
+              who ": empty map N=%d C=%d, %dx%d <-> %dx%d", N, C, H, W, OH, OW)
 
 extern "C" int adr_maxpool(int dtype, const void* x, int xcs, void* y, int ycs, uint8_t* arg, int N, int H, int W,
                            int C, int k, void* stream) {
@@ -514,6 +524,7 @@ extern "C" int adr_maxpool_bwd(int dtype, const void* dy, int dcs, const uint8_t
 extern "C" int adr_axis_mean(int dtype, const void* x, int xcs, int N, int H, int W, int C, void* oh, long ohn,
                              void* ow, long own, void* stream) {
   hipStream_t st = (hipStream_t)stream;
+  REQUIRE_MAP("axis_mean", N, H, W, C);
   const bool v = vec_ok(C, VW_OF(dtype), {xcs, ohn, own}, {x, oh, ow});
   const dim3 g = dim3(H + W, N);
   if (dtype == ADR_BF16) {
@@ -529,6 +540,7 @@ extern "C" int adr_axis_mean(int dtype, const void* x, int xcs, int N, int H, in
 extern "C" int adr_axis_mean_bwd(int dtype, const void* dh, long dhn, const void* dw, long dwn, void* dx, int ocs,
                                  int N, int H, int W, int C, int accumulate, void* stream) {
   hipStream_t st = (hipStream_t)stream;
+  REQUIRE_MAP("axis_mean_bwd", N, H, W, C);
   const bool v = vec_ok(C, VW_OF(dtype), {dhn, dwn, ocs}, {dh, dw, dx});
   const dim3 g = pool_grid((long)N * H * W, GOF(dtype, v, C));
   if (dtype == ADR_BF16) {
@@ -544,6 +556,7 @@ extern "C" int adr_axis_mean_bwd(int dtype, const void* dh, long dhn, const void
 extern "C" int adr_gate(int dtype, const void* x, int xcs, const void* ah, long ahn, const void* aw, long awn, void* o,
                         int ocs, int N, int H, int W, int C, void* stream) {
   hipStream_t st = (hipStream_t)stream;
+  REQUIRE_MAP("gate", N, H, W, C);
   const bool v = vec_ok(C, VW_OF(dtype), {xcs, ahn, awn, ocs}, {x, ah, aw, o});
   const dim3 g = pool_grid((long)N * H * W, GOF(dtype, v, C));
   if (dtype == ADR_BF16) {
@@ -560,6 +573,7 @@ extern "C" int adr_gate_bwd(int dtype, const void* x, int xcs, const void* ah, l
                             const void* dout, int dcs, void* dx, int ocs, void* dah, long dahn, void* daw, long dawn,
                             int N, int H, int W, int C, int accumulate, int zero_other, void* stream) {
   hipStream_t st = (hipStream_t)stream;
+  REQUIRE_MAP("gate_bwd", N, H, W, C);
   const bool v = vec_ok(C, VW_OF(dtype), {xcs, ahn, awn, dcs, ocs, dahn, dawn}, {x, ah, aw, dout, dx, dah, daw});
   const dim3 g = dim3(H + W, N);
   if (dtype == ADR_BF16) {
@@ -587,6 +601,7 @@ extern "C" int adr_gate_bwd(int dtype, const void* x, int xcs, const void* ah, l
 extern "C" int adr_adapool(int dtype, const void* x, int xcs, int N, int H, int W, int C, void* y, int ycs, int OH,
                            int OW, void* stream) {
   hipStream_t st = (hipStream_t)stream;
+  REQUIRE_RESIZE("adapool", N, H, W, C, OH, OW);
   const bool v = vec_ok(C, VW_OF(dtype), {xcs, ycs}, {x, y});
   const dim3 g = pool_grid((long)N * OH * OW, GOF(dtype, v, C));
   if (dtype == ADR_BF16) {
@@ -602,6 +617,7 @@ extern "C" int adr_adapool(int dtype, const void* x, int xcs, int N, int H, int 
 extern "C" int adr_adapool_bwd(int dtype, const void* dy, int dcs, int N, int H, int W, int C, void* dx, int ocs,
                                int OH, int OW, int accumulate, void* stream) {
   hipStream_t st = (hipStream_t)stream;
+  REQUIRE_RESIZE("adapool_bwd", N, H, W, C, OH, OW);
   const bool v = vec_ok(C, VW_OF(dtype), {dcs, ocs}, {dy, dx});
   const dim3 g = pool_grid((long)N * H * W, GOF(dtype, v, C));
   if (dtype == ADR_BF16) {
@@ -617,6 +633,7 @@ extern "C" int adr_adapool_bwd(int dtype, const void* dy, int dcs, int N, int H,
 extern "C" int adr_bilinear(int dtype, const void* x, int xcs, int N, int H, int W, int C, void* y, int ycs, int OH,
                             int OW, void* stream) {
   hipStream_t st = (hipStream_t)stream;
+  REQUIRE_RESIZE("bilinear", N, H, W, C, OH, OW);
   const bool v = vec_ok(C, VW_OF(dtype), {xcs, ycs}, {x, y});
   const dim3 g = pool_grid((long)N * OH * OW, GOF(dtype, v, C));
   if (dtype == ADR_BF16) {
@@ -632,6 +649,7 @@ extern "C" int adr_bilinear(int dtype, const void* x, int xcs, int N, int H, int
 extern "C" int adr_bilinear_bwd(int dtype, const void* dy, int dcs, int N, int H, int W, int C, void* dx, int ocs,
                                 int OH, int OW, int accumulate, void* stream) {
   hipStream_t st = (hipStream_t)stream;
+  REQUIRE_RESIZE("bilinear_bwd", N, H, W, C, OH, OW);
   const bool v = vec_ok(C, VW_OF(dtype), {dcs, ocs}, {dy, dx});
   const dim3 g = pool_grid((long)N * H * W, GOF(dtype, v, C));
   if (dtype == ADR_BF16) {
