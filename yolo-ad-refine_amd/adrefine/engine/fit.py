@@ -53,7 +53,7 @@ CSV_KEYS = ("epoch", "time", *TRAIN_KEYS, *METRIC_KEYS, *VAL_KEYS, *LR_KEYS)
 # cfg/default.yaml
 _DEFAULTS = dict(epochs=100, batch=16, imgsz=640, patience=100, optimizer="auto", cos_lr=False, close_mosaic=10,
                  lr0=0.01, lrf=0.01, momentum=0.937, weight_decay=0.0005, warmup_epochs=3.0, warmup_momentum=0.8,
-                 warmup_bias_lr=0.1, nbs=64, val=True, save=True, multi_scale=False, rect=False)
+                 warmup_bias_lr=0.1, nbs=64, val=True, save=True, multi_scale=False, rect=False, pretrained=True)
 
 
 def _arg(cfg, name):
@@ -131,6 +131,16 @@ def _default_loader(dataset, batch, shuffle, prefetch):
     return build_dataloader(dataset, batch, shuffle=shuffle, prefetch=prefetch)
 
 
+def _train_args(cfg):
+    """cfg as the checkpoint's train_args: a `pretrained` given as weights is recorded as True and a path as its
+    string, so the file holds the arguments, not a second copy of the weights, and still loads weights_only."""
+    args = dict(vars(cfg)) if hasattr(cfg, "__dict__") else {}
+    pre = args.get("pretrained")
+    if pre is not None and not isinstance(pre, bool):
+        args["pretrained"] = str(pre) if isinstance(pre, (str, Path)) else True
+    return args
+
+
 def _state_path(last):
     return Path(last).with_name("last_state.pt")
 
@@ -141,8 +151,10 @@ def fit(model, cfg, train_set, val_set, save_dir, resume=None, graphs=True, pref
     """Train `model` for cfg.epochs epochs on `train_set`, validating on `val_set` after each epoch.
 
     cfg: a namespace with the reference's training arguments (epochs, batch, imgsz, nbs, optimizer, lr0, lrf, momentum,
-    weight_decay, warmup_*, cos_lr, multi_scale, close_mosaic, patience, val, save; absent ones take
-    cfg/default.yaml's values) and the augmentation hyper-parameters close_mosaic edits. train_set / val_set: datasets
+    weight_decay, warmup_*, cos_lr, multi_scale, close_mosaic, patience, val, save, pretrained; absent ones take
+    cfg/default.yaml's values) and the augmentation hyper-parameters close_mosaic edits. pretrained: a path or a
+    state_dict is loaded with model.load before the validator copies the model (True / False / None load nothing:
+    there is no hub). train_set / val_set: datasets
     as data.build.build_yolo_dataset returns them (mode 'train' / 'val'). graphs=True captures the step into hipGraphs
     after the first eager step; graphs=False runs every step eagerly. on_epoch_end(epoch, row) is called with the
     epoch index and the dict written to results.csv; a true return value stops the run after that epoch's checkpoint.
@@ -167,6 +179,11 @@ def fit(model, cfg, train_set, val_set, save_dir, resume=None, graphs=True, pref
     csv = save_dir / "results.csv"
     last, best = wdir / "last.pt", wdir / "best.pt"
 
+    # get_model (models/yolo/detect/train.py:86-91): pretrained weights go into the model before anything copies it
+    # or caches its weights. True / False / None load nothing (there is no hub to fetch a default from)
+    pretrained = _arg(cfg, "pretrained")
+    if pretrained is not None and not isinstance(pretrained, bool) and not resume:  # a resume takes last.pt's weights
+        model.load(pretrained)
     loader = (loader_factory or _default_loader)(train_set, batch, True, prefetch)
     nb = len(loader)
     validator = (validator_factory or _default_validator)(model, cfg)  # copies the model before the trainer tags it
@@ -227,7 +244,7 @@ def fit(model, cfg, train_set, val_set, save_dir, resume=None, graphs=True, pref
             f.write(("" if csv.stat().st_size else csv_header()) + csv_row(epoch, time.time() - t0, row))
         stop = stop or stopper.update(epoch + 1, fitness) or final_epoch
         if _arg(cfg, "save") or final_epoch:
-            kw = dict(train_args=dict(vars(cfg)) if hasattr(cfg, "__dict__") else {}, train_metrics={**row})
+            kw = dict(train_args=_train_args(cfg), train_metrics={**row})
             if fitness is None:  # never validated: last.pt only
                 checkpoint.save_checkpoint(trainer, last, epoch, best_fitness=best_fitness, **kw)
             else:

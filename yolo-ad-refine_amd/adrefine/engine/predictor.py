@@ -50,10 +50,13 @@ class FusedPredictor:
         self.static_out = None
         # bf16 conv operands and the eval BatchNorm scale/shift computed once, not per batch (weights are fixed here)
         self.packs = K.PackCache(cache_bn_coefs=True)
+        from ..nn.tasks import register_dependent
+        register_dependent(model, self)  # DetectionModel.load then calls sync_weights: no predict with the old folded weights
 
     def sync_weights(self):
         """Repack the bf16 conv operands and recompute the eval BatchNorm coefficients after the model's weights or
-        running statistics changed (e.g. between training epochs)."""
+        running statistics changed (e.g. between training epochs, or DetectionModel.load). In place: a captured graph
+        reads the same buffers and needs no new capture."""
         self.packs.pack_all()
         self.packs.refresh_bn_coefs()
 

@@ -295,6 +295,8 @@ class FusedTrainer:
         self._key = None
         self._other = OrderedDict()
         self.packs = K.PackCache()
+        from ..nn.tasks import register_dependent
+        register_dependent(model, self)  # DetectionModel.load refuses to run under a live trainer
 
     def _build_table(self):
         tab = np.zeros(len(self.entries), dtype=_ENTRY)

@@ -12,6 +12,7 @@ import ast
 import contextlib
 import math
 import re
+import weakref
 from copy import deepcopy
 from pathlib import Path
 
@@ -20,6 +21,7 @@ import torch.nn as nn
 import yaml
 
 from .. import kernels as K
+from ..utils.torch_utils import intersect_dicts
 from .modules import block, conv, head
 
 # name -> class, mirroring the reference's tasks.py import list for the modules on this path
@@ -269,6 +271,32 @@ def route_layers(layers, save, x, y, start=0, cuts=(), uses=None):
     return x, bounds
 
 
+# model -> weak references to the objects built on its weights (FusedTrainer, FusedPredictor). Kept beside the
+# module, not on it, so a deepcopy of the model (the validator's) starts without any
+_DEPENDENTS = weakref.WeakKeyDictionary()
+
+
+def register_dependent(model, obj):
+    """Record that `obj` caches state derived from `model`'s weights; DetectionModel.load consults the list."""
+    _DEPENDENTS.setdefault(model, []).append(weakref.ref(obj))
+
+
+def _live_dependents(model):
+    refs = _DEPENDENTS.get(model, [])
+    live = [r() for r in refs]
+    refs[:] = [r for r, o in zip(refs, live) if o is not None]
+    return [o for o in live if o is not None]
+
+
+def _state_dict_of(w):
+    """w's state_dict when w is one (a non-empty mapping of names to tensors) or a module; else None."""
+    if isinstance(w, nn.Module):
+        return w.state_dict()
+    if isinstance(w, dict) and w and all(isinstance(k, str) and torch.is_tensor(v) for k, v in w.items()):
+        return w
+    return None
+
+
 class DetectionModel(nn.Module):
     """YOLO detection model (tasks.py:309-398). Compute dtype: float32 (parity) or bfloat16 (performance);
     parameters stay fp32. Input: float images (B, 3, H, W) in [0, 1] on a ROCm device."""
@@ -303,6 +331,56 @@ class DetectionModel(nn.Module):
         if isinstance(x, dict):
             return self.loss(x, *args, **kwargs)
         return self.predict(x, *args, **kwargs)
+
+    def load(self, weights, verbose=False):
+        """Transfer pretrained weights into this model (tasks.py:275-288): every tensor of `weights` whose key and
+        shape match this model's state_dict (utils.torch_utils.intersect_dicts) is loaded, in fp32; the others keep
+        their values — so a checkpoint of another `nc` loads everything but the class-dependent head tensors.
+        Returns (transferred, total), the two counts the reference logs.
+
+        `weights`: a state_dict; a checkpoint dict as engine.checkpoint writes it ('ema', else 'model', whichever
+        holds a state_dict or a module); an nn.Module (its state_dict, as fp32); or the path of such a checkpoint,
+        opened with checkpoint.load_checkpoint (weights_only=True: nothing in the file executes). A .pt file that
+        pickles the reference's classes cannot be opened here; export its state_dict on the reference side.
+
+        Call it before building a FusedTrainer on the model: the trainer's EMA starts from the weights it was built
+        on, so a load under a live trainer raises (to replace a running trainer's weights use its load_state_dict or
+        checkpoint.resume). A FusedPredictor built on the model is invalidated instead: its packed bf16 conv
+        operands and folded eval BatchNorm coefficients are rebuilt from the loaded weights, in the buffers its
+        captured graph reads, so the next predict uses the new weights."""
+        deps = _live_dependents(self)
+        busy = [d for d in deps if not hasattr(d, "sync_weights")]
+        if busy:
+            raise RuntimeError(f"DetectionModel.load under a live {type(busy[0]).__name__}: its EMA and optimizer "
+                               "state belong to the old weights. Load before building the trainer, or use the "
+                               "trainer's load_state_dict / checkpoint.resume")
+        if isinstance(weights, (str, Path)):
+            from ..engine.checkpoint import load_checkpoint
+            import pickle
+            try:
+                weights = load_checkpoint(weights)
+            except pickle.UnpicklingError as e:
+                raise TypeError(f"{weights}: not a weights_only checkpoint (a file that pickles model classes cannot "
+                                f"be opened here): pass a state_dict, or a checkpoint holding one ({e})") from None
+        sd = _state_dict_of(weights)
+        if sd is None and isinstance(weights, dict):
+            for key in ("ema", "model"):
+                sd = _state_dict_of(weights.get(key))
+                if sd is not None:
+                    break
+        if sd is None:
+            raise TypeError(f"DetectionModel.load: cannot take weights from {type(weights).__name__}: pass a "
+                            "state_dict, a checkpoint dict whose 'ema' or 'model' is a state_dict, an nn.Module, or "
+                            "the path of such a checkpoint")
+        own = self.state_dict()
+        csd = {k: (v.float() if v.is_floating_point() else v) for k, v in sd.items()}
+        csd = intersect_dicts(csd, own)
+        self.load_state_dict(csd, strict=False)
+        if verbose:
+            print(f"Transferred {len(csd)}/{len(own)} items from pretrained weights")
+        for d in deps:
+            d.sync_weights()
+        return len(csd), len(own)
 
     def predict(self, x, profile=False, visualize=False, augment=False, embed=None, cuts=()):
         if augment:
